@@ -11,6 +11,8 @@ all-gather + fixed tree inside libmcmcx.so when N > 1).  One bench "step" = --it
 iterations of every chain + that reduction.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full      # + CPU baseline, other configurations, adaptation timings
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + what the last timed step computed, as DIR/*.npy
     python bench.py --gpus 8                   # starts 8 ranks itself, one process per GPU
     python bench.py --workload c5              # the other BASELINE configurations: c2, c3, c5 (see WORKLOADS)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -27,14 +29,21 @@ own diagnostics and NO line -- unless `--allow-host-transport` was given: then (
 goes through the shared-memory segment and the line says so: `transport` "host", `rccl_error`, `rccl_ranks` 0.
 
 Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the engine's
-stream around every step-kernel launch of the timed region (mcmcx_kernel_time); `cpu_baseline`
+stream around every step-kernel launch of the timed region (mcmcx_kernel_time).  A plain run stops there: it sets up, warms up,
+times --steps steps and prints the line (`ms_per_step`: one timed step).  Everything else is measured with `--full` only: `cpu_baseline`
 times the real Fortran reference (oracle/_ref, kind "reference") or the C oracle (kind "port")
 on one host core and on all of them on the same target; `other_configs` (the LAST key, compact entries of <= 160 characters:
-value, frac, bound, issue, kernel, ms, share -- `--verbose` or gpurun_out/bench_other_configs.json for the long form) holds, at N = 1,
+value, frac, bound, issue, kernel, ms, share -- `--verbose` or the bench_other_configs.json the run writes for the long form) holds, at N = 1,
 a short run of each of the other BASELINE configurations in the same process after the headline's timed region and, at N > 1, a short
 run of c4 in POOLED mode on the same communicator -- the one collective that sits on the critical path (the pooled RAM tick every
 adaptint iterations) -- so that one scaling run also measures that; `roofline.others` mirrors [value, frac] of every BASELINE
-configuration; `roofline.traffic_source` says where the (stored, not live) PMC figure comes from; `device` identifies the box.
+configuration; `adaptation` times one adaptation where the timed iterations hold none; `device.rocm_smi` adds the clocks rocm-smi
+reports.  `roofline.traffic_source` says where the (stored, not live) PMC figure comes from; `device` identifies the box.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step (rank 0): the pooled moment vector
+(`pooled_moments`), the engine's totals (`totals`: delayed-rejection tries, stayed, downdates) and, for a fixed seeded sample of the
+rank's chains (`chain_ids`), their states (`theta`) and scalars (`scalars`: ss, prior, sigma2, alpha12), all float64.  The inputs are
+fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -271,7 +280,7 @@ def cpu_baseline(wl, ckw, pkw, per_it, label, target_seconds=12.0, all_cores=Tru
     return out
 
 
-def device_ident(L, dev):
+def device_ident(L, dev, smi=True):
     """What tells this box from another one of the pool in the JSON line: UUID, PCI bus id, clock limits (HIP) and, where
     rocm-smi answers, the clocks and the power cap it reports right now (best effort; never fatal)."""
     import ctypes
@@ -289,6 +298,8 @@ def device_ident(L, dev):
             out["pci"] = txt.split("pci ", 1)[1].split(",")[0]
     except Exception as ex:
         out["error"] = str(ex)[:120]
+    if not smi:
+        return out
     try:
         # (under rocprofv3 the profiler's preloaded library has initialised the GPU in every child too, and rocm-smi is a `#!/usr/bin/env python3`
         #  script: an exec after GPU initialisation, which the GPU boxes refuse -- skip it there)
@@ -399,9 +410,10 @@ class Watchdog:
 
 # ------------------------------------------------------------------ one configuration
 def run_config(wl, steps, warmup, rank, world, dev, comm, chains_per_gpu=0, its_per_step=0, method_opt=None, pooled=False,
-               replicas=False, start="default", transport="one GPU", scam_fast=False):
+               replicas=False, start="default", transport="one GPU", scam_fast=False, full=True, dump=False):
     """Time `steps` bench steps of configuration `wl` (after `warmup` untimed ones) on this rank's GPU; returns the pieces
-    of the JSON line on rank 0 (None elsewhere) and the pooled moment vector."""
+    of the JSON line on rank 0 (None elsewhere) and the pooled moment vector.  full: also time an adaptation where the timed
+    iterations hold none; dump: the line's `_outputs` holds what the last timed step computed (DUMP_SAMPLE chains of it)."""
     from mcmcf90_amd import engine_from_problem
     from mcmcf90_amd.workloads import problem
     n_local = chains_per_gpu or default_chains(wl, world)
@@ -413,7 +425,7 @@ def run_config(wl, steps, warmup, rank, world, dev, comm, chains_per_gpu=0, its_
     # afterwards, untimed for `value`, so that the line can say what an adaptation costs (N = 1 only)
     # (per-chain rotations at npar = 200, where an adaptation is one SVD per chain, time theirs on a second engine below: the first
     #  adaptation of this line has 100 rows for a 200 x 200 covariance -- rank-deficient, the pinned routine at its 60-sweep cap)
-    tick_probe = (world == 1 and it_end // adaptint_ == (warmup * ips) // adaptint_ and not (wl == "c5" and replicas))
+    tick_probe = (full and world == 1 and it_end // adaptint_ == (warmup * ips) // adaptint_ and not (wl == "c5" and replicas))
     next_tick = (it_end // adaptint_ + 1) * adaptint_
     if tick_probe:
         nsimu = next_tick + 1
@@ -462,6 +474,9 @@ def run_config(wl, steps, warmup, rank, world, dev, comm, chains_per_gpu=0, its_
     tries, stayed_all, downs_all = (float(x) for x in red[1])
     pooled_vec = eng.allreduce_moments(fetch=True)                                  # collective: every rank
     kname = eng.last_kernel()
+    outputs = None
+    if dump and rank == 0:
+        outputs = dump_sample(eng, n_local, pooled_vec, tot)
     tick_s = None
     if tick_probe and ckw.get("method", "dram") != "ram":
         eng.run(next_tick - 1); fence()
@@ -471,7 +486,7 @@ def run_config(wl, steps, warmup, rank, world, dev, comm, chains_per_gpu=0, its_
     eng.close()
     tick_note = None
     first_tick_s = second_tick_s = None
-    if wl == "c5" and replicas and not scam_fast and world == 1 and steps * ips < adaptint_:
+    if full and wl == "c5" and replicas and not scam_fast and world == 1 and steps * ips < adaptint_:
         # per-chain rotations at npar = 200: an adaptation is one SVD per chain.  Timed on a second engine of the same chains whose
         # covariance is full rank at the tick (initcmatn = npar: cmat0 carries weight; adaptint 10) -- what every adaptation after the
         # first is; the configuration's own first one (iteration 100 < npar rows: rank-deficient, the pinned routine runs to its
@@ -610,8 +625,26 @@ def run_config(wl, steps, warmup, rank, world, dev, comm, chains_per_gpu=0, its_
         "adaptation": adaptation,
         "pooled_check": {"chains": cnt, "max_abs_mean": float(np.max(np.abs(mean)))},
         "_cpu": (wl, ckw, pkw, per_it, "d=%d %s" % (d, method)),
+        "_outputs": outputs,
     }
     return res, pooled_vec
+
+
+DUMP_SAMPLE = 16384             # chains whose state --dump-outputs writes (all of them below this count)
+DUMP_SEED = 20240611
+
+
+def dump_sample(eng, n_local, pooled_vec, tot):
+    """What the timed path hands a caller after its last step: the pooled moments, the totals and, for a fixed seeded sample of
+    the rank's chains (at most 48 MB of states), theta and the per-chain scalars.  float64 throughout."""
+    d = eng.npar
+    k = int(min(n_local, DUMP_SAMPLE, 48e6 // (8 * (d + 4))))
+    ids = np.sort(np.random.default_rng(DUMP_SEED).choice(n_local, size=k, replace=False)) if k < n_local else np.arange(n_local)
+    return {"pooled_moments": np.asarray(pooled_vec, dtype=np.float64),
+            "totals": np.array([float(tot["drtries"]), float(tot["stayed"]), float(tot["downdates"])]),
+            "chain_ids": ids.astype(np.float64),
+            "theta": eng.theta()[ids],
+            "scalars": eng.scalars()[ids]}
 
 
 # the other BASELINE configurations, run briefly after the headline in the same process (N = 1): (key, run_config arguments)
@@ -669,6 +702,11 @@ def main():
     ap.add_argument("--verbose", action="store_true", help="`other_configs` entries in their long form (prose workload strings, every field) instead of the compact one")
     ap.add_argument("--one-gpu-dryrun", action="store_true",
                     help="debug: all ranks share GPU 0 and exchange through the host transport (checks the N>1 path on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the other BASELINE configurations (`other_configs`), the adaptation "
+                         "timings and rocm-smi's clocks (off by default: a plain run times its steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float64, < 64 MB in all")
     ap.add_argument("--dump-moments", default=None, help="debug: rank 0 writes the final pooled moment vector (float64) to this file")
     ap.add_argument("--plan", action="store_true", help="print how --gpus N would shard the configuration (one JSON line: chains and first chain id of "
                                                         "every rank, scaling mode) and exit; touches no GPU and starts no rank")
@@ -753,11 +791,12 @@ def main():
                                                "host transport, ranks share GPU 0" if a.one_gpu_dryrun else "RCCL all-gather + fixed tree")
     res, pooled_vec = run_config(a.workload, a.steps, a.warmup, rank, world, dev, comm, chains_per_gpu=a.chains_per_gpu,
                                  its_per_step=a.its_per_step, method_opt=a.method, pooled=a.pooled, replicas=a.replicas,
-                                 start=a.start, transport=transport, scam_fast=a.scam_fast)
+                                 start=a.start, transport=transport, scam_fast=a.scam_fast, full=a.full, dump=bool(a.dump_outputs))
     plain = a.workload == "c4" and not (a.pooled or a.method or a.start != "default" or a.its_per_step or a.replicas or a.scam_fast)
     line = None
     if rank == 0:
         cpu_args = res.pop("_cpu")
+        outputs = res.pop("_outputs")
         line = {
             "metric": res["metric"], "value": res["value"], "unit": "proposals/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": res["ms_per_step"], "higher_is_better": True,
@@ -770,10 +809,10 @@ def main():
             "rccl_ranks": rccl_ranks if (world > 1 and not a.one_gpu_dryrun and not rccl_failed) else (1 if world == 1 else 0),
             **({"rccl_error": rccl_failed} if rccl_failed else {}),
             "engine_sha": kernels_sha(),
-            "device": device_ident(L, dev),
+            "device": device_ident(L, dev, smi=a.full),
         }
     others, details = {}, {}
-    if not a.no_other_configs and plain and (world > 1 or not a.chains_per_gpu):
+    if a.full and not a.no_other_configs and plain and (world > 1 or not a.chains_per_gpu):
         # N = 1: the other BASELINE configurations, briefly, in this same process (builder-independent numbers for all of them);
         # N > 1: the pooled form of the headline on the same communicator (every rank runs it: its ticks are collective, so an
         # error there is not swallowed -- a rank that raised alone would leave its peers in the next gather)
@@ -823,7 +862,7 @@ def main():
         if others:
             # the driver stores `roofline` whole: every BASELINE configuration's [proposals/s, fraction of its roof] rides there too
             line["roofline"]["others"] = {k: [others[k]["value"], others[k]["frac"]] for k in HEADLINE_OTHERS if k in others and "value" in others[k]}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(*cpu_args)
         if others:
             line["other_configs"] = details if a.verbose else others       # LAST key of the line: the tail of stdout holds every configuration
@@ -835,6 +874,10 @@ def main():
                 pass
         if a.dump_moments:
             np.asarray(pooled_vec, dtype=np.float64).tofile(a.dump_moments)
+        if a.dump_outputs:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, arr in outputs.items():
+                np.save(os.path.join(a.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.barrier()

@@ -24,6 +24,18 @@ def available():
     return os.path.exists(EXE)
 
 
+ENGINE_DIR = os.path.join(os.path.dirname(_HERE), "mcmcf90_amd")
+
+
+def shim_env(**extra):
+    """Environment for the programs of oracle/_ref linked against the engine (one_shim, tc_*): this tree's mcmcf90_amd/ leads
+    LD_LIBRARY_PATH.  Their run path names libmcmcx.so relative to the binary ($ORIGIN), which the loader takes from the
+    binary's resolved location -- elsewhere than this tree when oracle/_ref is reached through a link."""
+    env = dict(os.environ, **extra)
+    env["LD_LIBRARY_PATH"] = ENGINE_DIR + (os.pathsep + env["LD_LIBRARY_PATH"] if env.get("LD_LIBRARY_PATH") else "")
+    return env
+
+
 def read_mat4(path):
     """MAT-v4 file written by matfiles.F90:66-126: 5 x int32 header, name, column-major doubles."""
     with open(path, "rb") as f:
@@ -276,7 +288,7 @@ def run_program_one(exe, cfg, prob, seeds, extra_nml="", seedfile=False, keep=Fa
         with open(os.path.join(d, "mcmcrun.nml"), "w") as f:
             f.write("&mcmcrun\n drstage = 1, isimu = 1, ieval = 0, nrej = 0, alpha12 = 0.0, sscrit = -1.0\n/\n")
         for s in seeds:
-            env = dict(os.environ, MCX_SEED=str(s), MCX_CHAIN="0", MKL_NUM_THREADS="1", MKL_THREADING_LAYER="SEQUENTIAL", OMP_NUM_THREADS="1")
+            env = shim_env(MCX_SEED=str(s), MCX_CHAIN="0", MKL_NUM_THREADS="1", MKL_THREADING_LAYER="SEQUENTIAL", OMP_NUM_THREADS="1")
             if seedfile:
                 open(os.path.join(d, "gfortran_seed.dat"), "w").write("%d\n" % s)
             p = subprocess.run([exe], cwd=d, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)

@@ -76,7 +76,8 @@ def test_reference_example_programs_link_unmodified():
     with tempfile.TemporaryDirectory() as d:
         for f in ("mcmcinit.nml", "data.dat", "mcmcpar.dat", "mcmccov.dat", "mcmcsigma2.dat"):
             shutil.copy(os.path.join("/root/reference/testcases", f), d)
-        p = subprocess.run([os.path.join(root, "oracle", "_ref", "tc_mcmcrun")], cwd=d, stdout=subprocess.PIPE,
+        from oracle.refrun import shim_env
+        p = subprocess.run([os.path.join(root, "oracle", "_ref", "tc_mcmcrun")], cwd=d, env=shim_env(), stdout=subprocess.PIPE,
                            stderr=subprocess.STDOUT, timeout=120)
         out = p.stdout.decode(errors="replace")
         assert p.returncode != 0 and "no HIP device" in out, out
@@ -105,7 +106,7 @@ def test_mcmc_main_one_without_a_gpu_stops_loudly_and_leaves_the_protocol_files_
         refrun.write_inputs(d, cfg, prob)
         nml = "&mcmcrun\n drstage = 1, isimu = 1, ieval = 0, nrej = 0, alpha12 = 0.0, sscrit = -1.0\n/\n"
         open(os.path.join(d, "mcmcrun.nml"), "w").write(nml)
-        p = subprocess.run([exe], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+        p = subprocess.run([exe], cwd=d, env=refrun.shim_env(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
         out = p.stdout.decode(errors="replace")
         assert p.returncode != 0 and "no HIP device" in out, out
         assert open(os.path.join(d, "mcmcrun.nml")).read() == nml

@@ -9,6 +9,7 @@ import tempfile
 import numpy as np
 import pytest
 from golden_util import load
+from oracle.refrun import shim_env
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -166,7 +167,7 @@ def test_reference_example_programs_run_unmodified(oracle, prog):
     z, cfg, prob = load("c1_shipped_nml", oracle)
     with tempfile.TemporaryDirectory() as d:
         _write_inputs(d, z, NML.split("&mcmcx")[0])
-        p = subprocess.run([exe], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+        p = subprocess.run([exe], cwd=d, env=shim_env(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
         assert p.returncode == 0, p.stdout.decode(errors="replace")
         chain = np.loadtxt(os.path.join(d, "chain.dat"), ndmin=2)
         s2 = np.loadtxt(os.path.join(d, "s2chain.dat"), ndmin=1)
@@ -213,7 +214,7 @@ def test_config1_verbatim_10000_iterations_with_delayed_rejection(oracle):
     assert cfg.nsimu == 10000 and cfg.drscale == 2.0 and cfg.doburnin == 1 and cfg.greedy == 1
     with tempfile.TemporaryDirectory() as d:
         _write_inputs(d, z, nml)
-        p = subprocess.run([exe], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+        p = subprocess.run([exe], cwd=d, env=shim_env(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
         assert p.returncode == 0, p.stdout.decode(errors="replace")
         chain = np.loadtxt(os.path.join(d, "chain.dat"), ndmin=2)
         s2 = np.loadtxt(os.path.join(d, "s2chain.dat"), ndmin=1)
@@ -315,7 +316,7 @@ def test_reference_gaussian_example_mcmcrun4():
         open(os.path.join(d, "mcmcinit.nml"), "w").write(nml)
         np.savetxt(os.path.join(d, "mcmctest_mu.dat"), mu[None, :])
         np.savetxt(os.path.join(d, "mcmctest_lam.dat"), np.linalg.inv(S))
-        p = subprocess.run([exe], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+        p = subprocess.run([exe], cwd=d, env=shim_env(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
         assert p.returncode == 0, p.stdout.decode(errors="replace")
         chain = np.loadtxt(os.path.join(d, "chain.dat"), ndmin=2)
     w = chain[:, -1]

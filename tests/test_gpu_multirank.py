@@ -163,7 +163,7 @@ def test_the_whole_gpus_n_json_path_with_as_many_ranks_as_the_box_allows(tmp_pat
     those of ONE rank with N x 64 chains bit for bit."""
     world, n = 4, 64
     common = ["--steps", "2", "--warmup", "1"]
-    many, mN = _bench(common + ["--gpus", str(world), "--one-gpu-dryrun", "--chains-per-gpu", str(n)], tmp_path, "many")
+    many, mN = _bench(common + ["--gpus", str(world), "--one-gpu-dryrun", "--chains-per-gpu", str(n), "--full"], tmp_path, "many")
     one, m1 = _bench(common + ["--gpus", "1", "--chains-per-gpu", str(world * n), "--no-other-configs"], tmp_path, "one")
     assert many["n_gpus"] == world and many["transport"] == "host" and many["rccl_ranks"] == 0
     assert many["config"]["total_chains"] == world * n and many["config"]["chains_per_gpu"] == n

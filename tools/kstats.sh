@@ -4,7 +4,7 @@ V=$1; shift
 REPO=$PWD; OUT=$REPO/gpurun_out/kstats_$$; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ -n "$V" ]; then export MCMCX_LIBRARY=$REPO/tools/_build/libmcmcx_$V.so; fi
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o kt -- python3 $REPO/bench.py --steps 6 --warmup 2 --no-cpu-baseline "$@" > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o kt -- python3 $REPO/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline "$@" > /dev/null 2>&1
 cd $REPO
 python3 - <<PY
 import csv,glob
