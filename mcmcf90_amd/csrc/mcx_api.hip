@@ -120,7 +120,6 @@ int mcmcx_create(const mcmcx_config *cfg_in, mcmcx_handle *out)
     if (c.device < 0 || c.device >= ndev) return fail(-10, "bad device ordinal");
     HIPCHK(hipSetDevice(c.device));
     mcmcx_engine *h = new mcmcx_engine();
-    h->sw.read();
     h->cfg = c; h->d = c.npar; h->P = c.npar * (c.npar + 1) / 2;
     h->ntiles = (c.nchains + 63) / 64; h->nlanes = h->ntiles * 64;
     h->dodr = (c.drscale > 0.0) ? 1 : 0; h->usesvd = (c.condmax > 0.0) ? 1 : 0; h->pooled = c.pooled ? 1 : 0;
@@ -297,7 +296,6 @@ int mcmcx_init(mcmcx_handle h)
     if (!h) return fail(-1, "null handle");
     if (h->inited) return fail(1, "Warning(mcmcinit): allready inited");            // MCMC_init.F90:24-27
     HIPCHK(hipSetDevice(h->cfg.device));
-    h->sw.read();                                    // the A/B switches as the environment has them now: fixed for the engine's life
     const mcmcx_config &c = h->cfg;
     const int d = h->d, P = h->P, T = h->ntiles;
     if ((int)h->par0.size() != d) return fail(-30, "user initialization error: par0 not set");
@@ -315,9 +313,10 @@ int mcmcx_init(mcmcx_handle h)
             std::to_string(h->mod_max_ny));
     if (h->tkind == TGT_EXPCOLS
         && h->tncols != ny) return fail(-36, "response-column target: mcmcx_set_sigma2nobs must give one sigma2 / nobs per column");
-    if (ny > 1 && h->pooled && (!fused_cols(h) || c.method == MCMCX_METHOD_SCAM))
-        return fail(-36, "nycol > 1 in pooled mode: the device-resident response-column target only, and not with method = 'scam'");
     if (h->tkind < 0) return fail(-31, "no target: the device engine needs mcmcx_set_target_*");
+    plan_kernels(h);                                 // which kernels run: decided here, once; what follows allocates as the plan says
+    if (ny > 1 && h->pooled && (!h->plan.fused_cols || c.method == MCMCX_METHOD_SCAM))
+        return fail(-36, "nycol > 1 in pooled mode: the device-resident response-column target only, and not with method = 'scam'");
     std::vector<double> Rp, Cp, Rfull, qstd0;
     int info = host_initial_R(d, h->cmat0, Rp, Cp);
     if (h->usesvd) {                                                                  // Cp (packed cmat0) is still needed
@@ -330,8 +329,7 @@ int mcmcx_init(mcmcx_handle h)
 
     EngineDev &E = h->E;
     E.d = d; E.P = P; E.ntiles = T;
-    // pooled RAM adapts on the host side: the kernels see a plain Metropolis step
-    E.method = (c.method == MCMCX_METHOD_RAM && !h->pooled) ? M_RAM : (c.method == MCMCX_METHOD_ER ? M_ER : M_DRAM);
+    E.method = kernel_method(h);
     E.usesvd = h->usesvd; E.doscam = (c.method == MCMCX_METHOD_SCAM) ? 1 : 0; E.condmax = c.condmax;
     E.scam_fast = c.scam_fast ? 1 : 0;
     E.Rf = E.R2f = E.qstd = E.Gw = E.Vw = nullptr;
@@ -341,29 +339,8 @@ int mcmcx_init(mcmcx_handle h)
     E.ny = ny; E.hs = d + ny; E.ssv = E.s2v = E.ss2v = nullptr; E.gshapev = nullptr;
     E.alphatarget = c.alphatarget; E.drscale = c.drscale; E.scalelimit = c.scalelimit; E.scalefactor = c.scalefactor;
     E.k0 = c.seed; E.chain_id0 = c.chain_id0;
-    E.dr_lds = (h->dodr && dr_fits_lds(h)) ? 1 : 0;
-    {   // plain AM / Metropolis / ER step kernel: state and scratch vectors in LDS (4 d x 512 bytes per wave) when that costs no
-        // occupancy -- eight waves per CU still fit (npar <= 10), or all tiles are resident at once anyway (few chains)
-        const char *ev = getenv("MCMCX_LDS_SCRATCH");                      // A/B switch: 0 = off
-        const size_t per_wave = (size_t)4 * d * 64 * sizeof(double);
-        const int per_cu = (int)((size_t)160 * 1024 / per_wave);
-        hipDeviceProp_t prop;
-        int cus = 256;
-        if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        const bool fits = per_cu >= 8 || (per_cu >= 1 && (long long)T <= (long long)per_cu * cus);
-        E.lds_scratch = (!h->pooled && !h->dodr && c.method != MCMCX_METHOD_RAM && c.method != MCMCX_METHOD_SCAM && fits && !(ev
-            && atoi(ev) == 0)) ? 1 : 0;
-        // ... and the packed factor with it (step_kernel_ldsr) where one column panel covers npar and state + factor of all tiles
-        // are resident at once: (2 npar + npar (npar + 1) / 2) x 512 bytes per wave, 38 KiB at npar = 10 = four waves per CU
-        const size_t per_wave_r = (size_t)(2 * d + P) * 64 * sizeof(double);
-        const int per_cu_r = (int)((size_t)160 * 1024 / per_wave_r);
-        const bool fits_r = per_cu_r >= 8 || (per_cu_r >= 1 && (long long)T <= (long long)per_cu_r * cus);
-        // MCMCX_LDS_SCRATCH=1: the state only (A/B)
-        if (E.lds_scratch && !h->usesvd && d <= TW && fits_r && !(ev && atoi(ev) == 1)) E.lds_scratch = 2;
-        // method='ram' (per-chain factor, Cholesky form): the factor DCHUD / DCHDD rewrite every iteration, and their rotations, in LDS for
-        // the launch where one column panel covers npar and all tiles are resident at once (step_kernel_ram_ldsr)
-        if (!h->pooled && c.method == MCMCX_METHOD_RAM && !h->usesvd && d <= RW && fits_r && !(ev && atoi(ev) == 0)) E.lds_scratch = 3;
-    }
+    E.dr_lds = h->plan.dr_lds ? 1 : 0;
+    E.lds_scratch = h->plan.lds_form;
     // target
     E.tgt.kind = phased(h) ? (int)TGT_HOST : h->tkind;   // the kernels know one phase-cut mode; who evaluates is the host's business
     E.tgt.b = h->tb; E.tgt.ndata = (int)h->tx.size(); E.tgt.ncols = h->tncols;
@@ -388,14 +365,9 @@ int mcmcx_init(mcmcx_handle h)
     // state
     const size_t L = (size_t)T * 64;
     if ((rc = dev_alloc(h, &E.theta, L * d))) return rc;
-    // the user's functions on the host and at most sixteen tiles: candidate, results and flags in mapped host memory -- a phase kernel's
-    // stores ARE the hand-over, the host's results are read by the next one in place (MCMCX_HOST_MAPPED=0: device buffers and copies)
-    h->host_mapped = h->tkind == TGT_HOST && T <= 16 && h->sw.host_mapped != 0;
-    // (RAM / SCAM use cs as sweep scratch)
-    h->cs_mapped = h->host_mapped && (c.method == MCMCX_METHOD_DRAM || c.method == MCMCX_METHOD_ER);
-    if ((rc = h->host_mapped ? host_alloc(h, &E.cand, L * d) : dev_alloc(h, &E.cand, L * d))) return rc;
+    if ((rc = h->plan.host_mapped ? host_alloc(h, &E.cand, L * d) : dev_alloc(h, &E.cand, L * d))) return rc;
     if ((rc = dev_alloc(h, &E.zs, L * 2 * d))) return rc;
-    if ((rc = h->cs_mapped ? host_alloc(h, &E.cs, L * 2 * d) : dev_alloc(h, &E.cs, L * 2 * d))) return rc;
+    if ((rc = h->plan.cs_mapped ? host_alloc(h, &E.cs, L * 2 * d) : dev_alloc(h, &E.cs, L * 2 * d))) return rc;
     E.xscr = nullptr;
     // step_kernel_pooled_dr_big's quadratic-form vectors; npar > 320: adapt_post_kernel's work vector
     if (((h->pooled && h->dodr) || d > 320) && (rc = dev_alloc(h, &E.xscr, L * 2 * d))) return rc;
@@ -406,9 +378,7 @@ int mcmcx_init(mcmcx_handle h)
     if (!h->pooled && (rc = dev_alloc(h, &E.R, L * P, false))) return rc;          // pooled: one shared factor instead
     if ((rc = dev_alloc(h, &E.basetheta, L * d))) return rc;
     if (h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM) {     // pooled SCAM: one rotation for every chain
-        // npar > 240: slower, not refused -- scam_kernel / scam_mw_kernel on per-chain copies
-        h->scam_replicated = scam_pooled_lds(d) > 160 * 1024;
-        if (h->scam_replicated) {
+        if (h->plan.scam_replicated) {
             if ((rc = dev_alloc(h, &E.Rf, L * (size_t)d * d, false))) return rc;
             if ((rc = dev_alloc(h, &E.qstd, L * d))) return rc;
         } else if ((rc = dev_alloc(h, &h->d_sharedU, 2 * shared_u_stride(h) + d, false))) return rc;
@@ -422,7 +392,7 @@ int mcmcx_init(mcmcx_handle h)
         if (c.method != MCMCX_METHOD_RAM) {                 // work space of the adaptation's SVD; RAM never refactors
             if ((rc = dev_alloc(h, &E.Gw, L * DD))) return rc;
             if ((rc = dev_alloc(h, &E.Vw, L * DD))) return rc;
-            if (svd_blocked(h) && (c.doadapt != 0 || c.doburnin != 0)) {      // chain-major copies for svd_blocked_kernel
+            if (h->plan.svd_blocked) {                  // chain-major copies for svd_blocked_kernel
                 if ((rc = dev_alloc(h, &h->d_Gc, L * DD, false))) return rc;
                 if ((rc = dev_alloc(h, &h->d_Vc, L * DD, false))) return rc;
                 if ((rc = dev_alloc(h, &h->d_svc, L * d, false))) return rc;
@@ -475,7 +445,7 @@ int mcmcx_init(mcmcx_handle h)
     if (h->pooled) {
         if ((long long)c.nchains * (h->comm ? h->comm->nranks
             : 1) < 2) return fail(-8, "pooled mode needs at least 2 chains over all ranks");
-        if (phase_cut(h) || (fused_cols(h) && c.method == MCMCX_METHOD_SCAM))
+        if (phase_cut(h) || (h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM))
             return fail(-8, "pooled mode needs one of the single-launch device targets (gauss, banana, expdata, expcols; scam: not expcols)");
         if ((rc = dev_alloc(h, &h->d_sharedR, (size_t)P, false))) return rc;
         HIPCHK(hipMemcpy(h->d_sharedR, Rp.data(), (size_t)P * 8, hipMemcpyHostToDevice));
@@ -489,7 +459,8 @@ int mcmcx_init(mcmcx_handle h)
     }
     E.hev = E.hx = nullptr;
     if (phased(h)) {
-        if ((rc = h->host_mapped ? host_alloc(h, &E.hev, L * (NHE - 1 + ny)) : dev_alloc(h, &E.hev, L * (NHE - 1 + ny)))) return rc;
+        const size_t nhev = L * (NHE - 1 + ny);
+        if ((rc = h->plan.host_mapped ? host_alloc(h, &E.hev, nhev) : dev_alloc(h, &E.hev, nhev))) return rc;
         if (ny > 1) {
             if ((rc = dev_alloc(h, &E.ssv, L * ny))) return rc;
             if ((rc = dev_alloc(h, &E.s2v, L * ny))) return rc;
@@ -499,49 +470,14 @@ int mcmcx_init(mcmcx_handle h)
             for (int j = 0; j < ny; ++j) gs[j] = c.N0 / 2.0 + (double)h->nobsv[j] / 2.0;
             if ((rc = dev_upload(h, &E.gshapev, gs))) return rc;
         }
-        if ((rc = h->host_mapped ? host_alloc(h, &E.hx, L * NHX) : dev_alloc(h, &E.hx, L * NHX))) return rc;
+        if ((rc = h->plan.host_mapped ? host_alloc(h, &E.hx, L * NHX) : dev_alloc(h, &E.hx, L * NHX))) return rc;
     }
     E.accmask = nullptr;
     if (c.record_accept && (rc = dev_alloc(h, &E.accmask, (size_t)c.nsimu * T))) return rc;
-    // the lane-group step kernel where it covers the configuration: MCMCX_GROUP = 1 / 0 forces it on / off (A/B, tests)
-    h->group_d4 = 0;
-    if (group_covers(h)) {
-        const char *ev = getenv("MCMCX_GROUP");
-        int ex = 0;
-        const bool pow2 = h->dodr && c.drscale > 0.0 && std::frexp(c.drscale, &ex) == 0.5 && ex > -64 && ex < 64;
-        // (the power-of-two form keeps iC in LDS: above npar 24 that leaves fewer waves per CU than the register form's four)
-        const int drm = !h->dodr ? 0 : (pow2 && d <= 24 && !(getenv("MCMCX_GROUP_DR2") && atoi(getenv("MCMCX_GROUP_DR2")) == 0)) ? 2 : 1;
-        const char *gwe = getenv("MCMCX_GROUP_GW");                                             // (4 / 16: A/B, tests)
-        const int gw = (d <= 16 && gwe) ? (atoi(gwe) == 4 ? 4 : 16) : group_width(h);
-        const bool on = ev ? atoi(ev) != 0 : group_wins(h, drm, gw);
-        if (on) h->group_d4 = d <= 32 ? ((d + 3) & ~3) : ((d + 7) & ~7);
-        if (h->group_d4 && (E.hist || E.accmask) && (rc = dev_alloc(h, &h->d_accb, L * (size_t)GROUP_MAXSEG))) return rc;
-        if (h->group_d4) {
-            h->group_gw = gw;
-            h->group_drm = drm;
-            h->group_check_due = true;
-            if (h->group_drm == 2 && (rc = dev_alloc(h, &h->d_gflag, 1))) return rc;
-        }
-    }
-    // method = 'ram' with few chains on the lane-group kernel (MCMCX_RAM_GROUP = 1 / 0: always where it covers / never; A/B, tests)
-    h->ram_group_d4 = 0;
-    if (ram_group_covers(h)) {
-        const char *rg = getenv("MCMCX_RAM_GROUP");
-        if (!rg) rg = getenv("MCMCX_GROUP");               // (the kernel-family switch of the tests covers it too)
-        if (rg ? atoi(rg) != 0 : ram_group_wins(h)) {
-            h->ram_group_d4 = d <= 16 ? 16 : d <= 32 ? 32 : d <= 56 ? 56 : 64;
-            if ((E.hist || E.accmask) && (rc = dev_alloc(h, &h->d_accb, L * (size_t)GROUP_MAXSEG))) return rc;
-        }
-    }
-    // the adaptation's factorisation (Cholesky branch) with the matrices in LDS (tile_factor_kernel): any chain count, npar <= 32 -- config
-    // 3's size (npar 20, delayed rejection, 262144 chains): 2.11 -> 1.44 ms per tick, bound by VALU issue (~25 instructions per inner step
-    // of four chains). Above npar 32 adapt_post_kernel's 8 x 8 register blocks stay: at npar 50 x 1 048 576 chains they stream the matrices
-    // ~5.6 times (16.0 ms) and still beat the LDS form, whose three waves per CU issue ~15 x the instructions per chain (35.2 ms;
-    // profiles/r05_a/tick_ab.txt). MCMCX_TILE_FACTOR = 0 / 1: never / up to npar 64 (test switch: both forms on one problem).
-    {
-        const char *tf = getenv("MCMCX_TILE_FACTOR");
-        h->tile_factor = am && !h->usesvd && d <= ((tf && atoi(tf) == 1) ? 64 : 32) && !(tf && atoi(tf) == 0);
-    }
+    // the lane-group kernels: accept bytes of a launch; the range flag of the power-of-two delayed-rejection form
+    if ((h->plan.group_d4 || h->plan.ram_group_d4) && (E.hist || E.accmask)
+        && (rc = dev_alloc(h, &h->d_accb, L * (size_t)GROUP_MAXSEG))) return rc;
+    if (h->plan.group_d4 && h->plan.group_drm == 2 && (rc = dev_alloc(h, &h->d_gflag, 1))) return rc;
     // 1/simuind**nuparam, computed like the reference: real(simuind) is default REAL (MCMC_run_ram.F90:166)
     {
         std::vector<double> rs((size_t)c.nsimu + 2, 0.0);
@@ -584,8 +520,7 @@ int mcmcx_init(mcmcx_handle h)
                 if (h->usesvd) { h->pool_R2 = Rfull; for (auto &v : h->pool_R2) v = v / c.drscale; } else h->pool_R2 = R2p;
                 if ((rc = dev_alloc(h, &h->d_sharedR2, h->usesvd ? (size_t)((d + 3) & ~3) * d + PWS : (size_t)P, false))) return rc;
                 if ((rc = dev_alloc(h, &h->d_sharediC, (size_t)P, false))) return rc;
-                if (c.method == MCMCX_METHOD_DRAM && h->d_sharedRT && pooled_mfma_lds(d) <= 160 * 1024 &&
-                    !(h->sw.pooled_scalar > 0)) {          // the second stage on the matrix cores too
+                if (h->plan.pooled_dr_mfma) {
                     if ((rc = dev_alloc(h, &h->d_sharedR2T, (size_t)((d + 3) & ~3) * d + PWS, false))) return rc;
                     if ((rc = dev_alloc(h, &h->d_sharediCd, (size_t)((d + 3) & ~3) * d + PWS, false))) return rc;
                 }
@@ -653,7 +588,8 @@ static int run_impl(mcmcx_handle h, int32_t upto)
     HIPCHK(hipSetDevice(h->cfg.device));
     const mcmcx_config &c = h->cfg;
     if (upto > c.nsimu) upto = c.nsimu;
-    const int maxseg = (h->group_d4 || h->ram_group_d4) ? GROUP_MAXSEG : (c.method == MCMCX_METHOD_RAM && !h->pooled) ? 4096 : 1 << 30;
+    const int maxseg = (h->plan.group_d4 || h->plan.ram_group_d4) ? GROUP_MAXSEG
+                       : (c.method == MCMCX_METHOD_RAM && !h->pooled) ? 4096 : 1 << 30;
     int it = h->simuind + 1;
     // Several ranks that meet in this engine's ticks (pooled mode with a communicator): a rank that left the loop alone --
     // on a signal it happened to see first, or on an error of its own -- would leave its peers waiting in the next gather.

@@ -1,15 +1,6 @@
 // mcx_host_adapt.hpp -- the adaptation tick's launch sequence (MCMC_adapt.F90:12-230) and its schedule.
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch, mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
-// the adaptation's SVD one workgroup per chain (mcx_svd.hpp) where its rings and row groups are instantiated
-static bool svd_blocked(const mcmcx_engine *h)
-{
-    if (!h->usesvd || h->pooled || h->cfg.method == MCMCX_METHOD_RAM) return false;
-    // test switch: the lane SVD (the engine's form below npar 48 and above 256)
-    if (h->sw.svd_lane > 0) return false;
-    // (its rings and row groups are instantiated up to npar 256)
-    return h->d >= 48 && h->d <= 256;
-}
 static void launch_adapt(mcmcx_engine *h, int it, int mode)
 {
     // one d-vector / the Cholesky's diagonal block (18 kB: eight waves per CU up to npar 36)
@@ -18,8 +9,7 @@ static void launch_adapt(mcmcx_engine *h, int it, int mode)
     // covmat's batch branch in blocks (adapt_covb_*): the AP window at every adaptation; with initcmatn = 0 the first AM adaptation and
     // the greedy restarts.  Which lanes take it is the lanes' own business (ADF_BATCH); a tick that cannot hold any skips the launches.
     const bool ap = (mode & AD_AM) && h->cfg.adapthist > 1;
-    // (test switch: covmat_rows, the lane form)
-    const int batch_done = (!(h->sw.cov_batch_rows > 0) &&
+    const int batch_done = (h->plan.cov_batch &&
                             (ap || (h->cfg.initcmatn == 0 && ((mode & AD_FIRST) || ((mode & AD_BURN) && h->cfg.greedy != 0))))) ? 1 : 0;
     if (batch_done) {
         const int n10 = (h->d + TD - 1) / TD, noff = n10 * (n10 - 1) / 2;
@@ -37,7 +27,7 @@ static void launch_adapt(mcmcx_engine *h, int it, int mode)
             if (noff > 0) hipLaunchKernelGGL(adapt_cov_off_kernel, dim3(g8 * noff), dim3(64), 0, h->stream, h->E, it, mode, noff);
         }
     }
-    if (!h->d_Gc) {
+    if (!h->plan.svd_blocked) {
         if (lds > 160 * 1024) {                             // npar > 320: the work vector in global scratch (slower; no limit)
             if (h->usesvd) hipLaunchKernelGGL((adapt_post_kernel<true, true>), dim3(h->ntiles), dim3(64), 0, h->stream, h->E, it, mode, 0,
                 (uint8_t *)nullptr, batch_done);
@@ -47,7 +37,7 @@ static void launch_adapt(mcmcx_engine *h, int it, int mode)
         }
         if (h->usesvd) hipLaunchKernelGGL(adapt_post_kernel<true>, dim3(h->ntiles), dim3(64), lds, h->stream, h->E, it, mode, 0,
             (uint8_t *)nullptr, batch_done);
-        else if (h->tile_factor) {
+        else if (h->plan.tile_factor) {
             // dpotf2 (+ dtrti2 / dlauu2 with delayed rejection) with the packed matrices of 4 NW neighbouring chains in LDS, read and
             // written once (mcx_group.hpp: tile_factor_kernel); adapt_post_kernel keeps the covariance bookkeeping (phase 3)
             hipLaunchKernelGGL(adapt_post_kernel<false>, dim3(h->ntiles), dim3(64), lds, h->stream, h->E, it, mode, 3, (uint8_t *)nullptr,

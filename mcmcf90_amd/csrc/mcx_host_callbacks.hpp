@@ -26,8 +26,8 @@ static int host_eval(mcmcx_engine *h, const double *dev_src, int stride_k, bool 
     }
     const size_t L = (size_t)T * 64;
     const int ny = h->ny, nhe = NHE - 1 + ny;
-    const bool src_mapped = h->host_mapped && (dev_src == h->E.cand || h->cs_mapped);
-    const bool mapped = h->host_mapped;                  // flags and results in place
+    const bool src_mapped = h->plan.host_mapped && (dev_src == h->E.cand || h->plan.cs_mapped);
+    const bool mapped = h->plan.host_mapped;                 // flags and results in place
     if ((!src_mapped && h->h_cand.resize(L * stride_k)) || (!mapped && (h->h_ev.resize(L * nhe) || (use_stage2_flag
         && h->h_hx.resize(L * NHX)))))
         return fail(-100, "host callbacks: no page-locked memory for the candidates");
@@ -113,7 +113,7 @@ static int host_iteration(mcmcx_engine *h, int it, bool fuse_next)
     const dim3 g(h->ntiles), b(64);
     const double *rs = h->d_ramscale + it, *rs0 = h->d_ramscale;
     const size_t lds = lds_step(h);
-    const bool fuse = h->sw.host_fuse != 0;
+    const bool fuse = h->plan.host_fuse;
     fuse_next = fuse_next && fuse;
     const bool p0_done = h->p0_done;
     h->p0_done = false;

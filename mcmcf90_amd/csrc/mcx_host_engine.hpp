@@ -20,12 +20,12 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 // The test switches (tests, tools): each FORCES one of two kernel forms that the engine also chooses by itself for some configuration -- so
 // that the parity tests can run both forms on the same small problem.  None selects a form the engine would never take (those live in
-// tools/variants, outside this library).  Read from the environment ONCE per engine, at mcmcx_create and again at mcmcx_init -- never at
-// launch time.  -1 = not set.
+// tools/variants, outside this library).  Read from the environment once per engine, by plan_kernels at mcmcx_init (mcx_host_launch.hpp),
+// the only code that reads them -- never at launch time.  -1 = not set.
 struct mcx_switches {
     int pooled_mfma_dr_min = -1, pooled_scalar = -1, dr_big = -1, scam_pooled_16 = -1, scam_fast_lanes = -1, scam_waves = -1,
         svd_lane = -1, cov_batch_rows = -1, ram_wide = -1, pooled_waves = -1, pooled_ks = -1, cols_phased = -1, host_mapped = -1,
-            host_fuse = -1;
+            host_fuse = -1, lds_scratch = -1, group = -1, group_dr2 = -1, group_gw = -1, ram_group = -1, tile_factor = -1;
     static int get(const char *name) { const char *e = getenv(name); return e ? atoi(e) : -1; }
     void read()
     {
@@ -34,16 +34,50 @@ struct mcx_switches {
         scam_waves = get("MCMCX_SCAM_WAVES"); svd_lane = get("MCMCX_SVD_LANE"); cov_batch_rows = get("MCMCX_COV_BATCH_ROWS");
         ram_wide = get("MCMCX_RAM_WIDE"); pooled_waves = get("MCMCX_POOLED_WAVES"); pooled_ks = get("MCMCX_POOLED_KS");
         cols_phased = get("MCMCX_COLS_PHASED"); host_mapped = get("MCMCX_HOST_MAPPED"); host_fuse = get("MCMCX_HOST_FUSE");
+        lds_scratch = get("MCMCX_LDS_SCRATCH"); group = get("MCMCX_GROUP"); group_dr2 = get("MCMCX_GROUP_DR2");
+        group_gw = get("MCMCX_GROUP_GW"); ram_group = get("MCMCX_RAM_GROUP"); tile_factor = get("MCMCX_TILE_FACTOR");
     }
+};
+// the plain lane step's LDS form (EngineDev::lds_scratch): nothing, the state and scratch vectors (step_kernel_ldsv), those and the packed
+// factor (step_kernel_ldsr); method = 'ram': the factor and its rotations (step_kernel_ram_ldsr)
+enum LdsForm { LDS_NONE = 0, LDS_STATE = 1, LDS_STATE_R = 2, LDS_RAM_R = 3 };
+struct KernelEntry;
+// Which kernel forms the engine runs.  Decided ONCE, by plan_kernels at mcmcx_init (mcx_host_launch.hpp), from the configuration, the
+// problem's shape, the target kind, the switches and the CU count -- never from what was allocated; mcmcx_init allocates as it says and
+// every launcher reads it.
+struct KernelPlan {
+    int lds_form = LDS_NONE;
+    bool dr_lds = false;                // delayed rejection's work vectors fit LDS (EngineDev::dr_lds)
+    bool dr_vectors_in_lds = false;     // ... and its second stage keeps two vectors there (step_kernel_dr against step_kernel_dr_big)
+    // lane-group step kernel (mcx_group.hpp): npar rounded up (0 = not this kernel), delayed-rejection mode, lanes per chain
+    int group_d4 = 0, group_drm = 0, group_gw = 16;
+    // method = 'ram' on group_ram_kernel (mcx_group_ram.hpp): npar rounded up to its instantiation, 0 = not
+    int ram_group_d4 = 0;
+    bool tile_factor = false;           // the adaptation's Cholesky branch through tile_factor_kernel (npar <= 64)
+    bool svd_blocked = false;           // the adaptation's SVD one workgroup per chain (svd_blocked_kernel and its sweeps)
+    bool cov_batch = true;              // the covariance's batch branch in blocks (adapt_covb_*) where it applies
+    bool scam_replicated = false;       // pooled SCAM above npar 240: the shared rotation copied to every chain, the per-chain kernels run
+    // host callbacks with few chains: the exchange vectors in page-locked host memory the device reads and writes directly (no copies
+    // between the phases)
+    bool host_mapped = false, cs_mapped = false;
+    bool host_fuse = true;              // host callbacks: the next iteration's proposal rides in this iteration's last launch
+    bool fused_cols = false;            // the response-column target's phases in one launch per segment (step_kernel_cols)
+    bool pooled_mfma = false;           // pooled mode on the matrix cores (pooled_mfma_kernel and kin)
+    bool pooled_dr_mfma = false;        // ... with delayed rejection: the dense R2 / iC tables (pooled_mfma_kernel<true>)
+    bool pooled_two_waves = false, pooled_forty_rows = false;
+    bool ram_wide = false;              // method = 'ram' above RAM_SMALL_MAX through step_kernel_ram_wide
+    bool scam_pooled12 = false, scam_fast_tile = false; int scam_waves = 1;
+    const KernelEntry *step = nullptr;  // what launch_step runs: a GROUP_TABLE entry when group_d4, a STEP_TABLE one otherwise
+    const KernelEntry *scam = nullptr;  // what launch_scam runs
 };
 struct mcmcx_engine {
     mcmcx_config cfg;
-    mcx_switches sw;
+    KernelPlan plan;
     int d = 0, P = 0, ntiles = 0, nlanes = 0;
     int dodr = 0, usesvd = 0;
     bool inited = false;
     int simuind = 0;
-    const char *last_kernel = "";       // name of the sampling kernel launch_step / launch_scam chose last (mcmcx_last_kernel)
+    const char *last_kernel = "";       // name of the sampling kernel launch_step / launch_scam ran last (mcmcx_last_kernel)
     std::string launch_err;             // set by a launcher that found no kernel for the configuration: the run fails with it
     // host copies of the problem
     std::vector<double> par0, cmat0;                 // cmat0 col-major d*d
@@ -88,13 +122,7 @@ struct mcmcx_engine {
     bool p0_done = false;
     // a host-callback iteration failed half way: the chains' stream positions are undefined, later runs are refused
     bool failed = false;
-    // host callbacks with few chains: the exchange vectors live in page-locked host memory the device reads and writes directly (no copies
-    // between the phases)
-    bool host_mapped = false, cs_mapped = false;
     std::vector<void *> hallocs;
-    // pooled SCAM above npar 240 (the tile kernels' LDS vector does not fit): the shared rotation copied to every chain, the per-chain
-    // kernels run
-    bool scam_replicated = false;
     // pooled AM on the matrix cores: dense R, M[s*d + o] = R(s,o), zero below the diagonal and in the pad rows
     double *d_sharedRT = nullptr;
     double *d_sharedR2T = nullptr, *d_sharediCd = nullptr;   // ... with delayed rejection: R2 in the same form, iC dense and symmetric
@@ -115,11 +143,8 @@ struct mcmcx_engine {
     // blocked SVD of the adaptation (large npar)
     double *d_Gc = nullptr, *d_Vc = nullptr, *d_svc = nullptr; uint8_t *d_need = nullptr, *d_state = nullptr; int *d_anyrot = nullptr;
     int wcap = 0;
-    bool tile_factor = false;           // the adaptation's Cholesky branch through tile_factor_kernel (npar <= 64)
-    // method = 'ram' on group_ram_kernel (mcx_group_ram.hpp): npar rounded up to its instantiation, 0 = not
-    int ram_group_d4 = 0;
-    // lane-group step kernel (mcx_group.hpp): npar rounded up to four when it is the one to launch; accept bytes of a launch
-    int group_d4 = 0, group_drm = 0, group_gw = 16; bool group_check_due = true; int *d_gflag = nullptr; uint8_t *d_accb = nullptr;
+    // lane-group kernels: the factors were rewritten since the last range check (DR2), its flag, the accept bytes of a launch
+    bool group_check_due = true; int *d_gflag = nullptr; uint8_t *d_accb = nullptr;
     // MCMC_run1: the caller evaluates; exchange vectors of run1_kernel
     bool external = false; double *d_r1 = nullptr; std::vector<double> h_r1;
     // timing of the step kernel

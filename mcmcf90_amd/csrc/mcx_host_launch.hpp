@@ -1,5 +1,6 @@
-// mcx_host_launch.hpp -- which sampling kernel runs: cover predicates, the three selection tables (step / group / scam) and their
-// launchers, the shared tables' uploads.
+// mcx_host_launch.hpp -- which kernels run: the three selection tables (step / group / scam) and their launchers, the shared tables'
+// uploads, and plan_kernels -- the one place that reads the test switches and holds the "where it wins" rules, run once at mcmcx_init;
+// its KernelPlan (mcx_host_engine.hpp) is all the launchers and mcmcx_init consult.
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch,
 // mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
@@ -12,7 +13,7 @@ static size_t pooled_mfma_lds(int d)
     const size_t rows = (nt <= 4) ? std::max(d4, 4 * nt) : d4 + 16 * nt + 4 * nt;
     return rows * 64 * sizeof(double);
 }
-static bool pooled_use_mfma(const mcmcx_engine *h)
+static bool pooled_use_mfma(const mcmcx_engine *h, const mcx_switches &sw)
 {
     // (SCAM has its own)
     if (!h->pooled || (h->cfg.method != MCMCX_METHOD_DRAM && h->cfg.method != MCMCX_METHOD_RAM
@@ -20,53 +21,63 @@ static bool pooled_use_mfma(const mcmcx_engine *h)
     // DR: with its dense tables, and above
     if (h->dodr) {
         // npar 20 (8.3e8 against 8.9e8 iterations/s
-        if (h->cfg.method != MCMCX_METHOD_DRAM || !h->d_sharedR2T) return false;
         // for the lane kernel with its LDS vectors at 20;
         int dmin = 21;
         // 32: 5.6e8 / 2.5e8, 50: 3.2e8 / 0.8e8)
-        if (h->sw.pooled_mfma_dr_min >= 0) dmin = h->sw.pooled_mfma_dr_min;
+        if (sw.pooled_mfma_dr_min >= 0) dmin = sw.pooled_mfma_dr_min;
         if (h->d < dmin) return false;
     }
-    if (h->sw.pooled_scalar > 0) return false;                                         // A/B switch for tests: the lane-per-chain kernel
+    if (sw.pooled_scalar > 0) return false;                                            // A/B switch for tests: the lane-per-chain kernel
     return pooled_mfma_lds(h->d) <= 160 * 1024;
 }
 // iteration cut at the evaluations
 static bool phased(const mcmcx_engine *h) { return h->tkind == TGT_HOST || h->tkind == TGT_EXPCOLS || h->tkind == TGT_MODULE; }
-// ... except where the DEVICE evaluates between the phases (the response-column target): the phases fused into one launch per segment
-// (step_kernel_cols); MCMCX_COLS_PHASED=1 keeps the separate launches (A/B, tests)
-static bool fused_cols(const mcmcx_engine *h) { return h->tkind == TGT_EXPCOLS && !(h->sw.cols_phased > 0); }
-static bool phase_cut(const mcmcx_engine *h) { return phased(h) && !fused_cols(h); }
+// ... except where the DEVICE evaluates between the phases (the response-column target): KernelPlan::fused_cols
+static bool phase_cut(const mcmcx_engine *h) { return phased(h) && !h->plan.fused_cols; }
+// the step kernels' method class (EngineDev::method): pooled RAM adapts on the host side, the kernels see a plain Metropolis step
+static int kernel_method(const mcmcx_engine *h)
+{
+    const int m = h->cfg.method;
+    return (m == MCMCX_METHOD_RAM && !h->pooled) ? M_RAM : (m == MCMCX_METHOD_ER ? M_ER : M_DRAM);
+}
 static size_t lds_bytes(const mcmcx_engine *h) { return (size_t)h->d * 64 * sizeof(double) * 2; }   // adapt / DR work vectors
 static bool dr_fits_lds(const mcmcx_engine *h) { return lds_bytes(h) <= 160 * 1024; }          // npar <= 160
-static size_t lds_step(const mcmcx_engine *h) { return (h->dodr && dr_fits_lds(h)) ? lds_bytes(h) : 0; }
+static size_t lds_step(const mcmcx_engine *h) { return h->plan.dr_lds ? lds_bytes(h) : 0; }
 // step_kernel_dr keeps the second stage's two vectors in LDS, step_kernel_dr_big in global scratch.  LDS pays while eight waves
 // still fit a CU (npar <= 20: 6.9e8 against 6.0e8 iterations/s at 20); beyond, the waves it costs are worth more than the bytes
 // it saves (npar 24: 3.1e8 against 4.1e8, 64: 3.2e7 / 4.6e7, 100: 0.8e7 / 1.7e7 -- tools/dr_sweep.py)
 // (the pooled form, whose factors come through the scalar cache, is bound by that latency rather than by waves: LDS down to four
 //  waves per CU -- npar 32: 2.5e8 against 2.2e8, 50: 7.4e7 / 8.1e7, 100: 0.8e7 / 1.3e7 -- tools/pooled_dr_probe.py)
-static bool dr_vectors_in_lds(const mcmcx_engine *h, int min_waves = 8)
+static bool dr_vectors_in_lds(const mcmcx_engine *h, const mcx_switches &sw, int min_waves)
 {
     if (!dr_fits_lds(h)) return false;
-    if (h->sw.dr_big >= 0) return h->sw.dr_big == 0;                                  // A/B switch for tests: 1 = global scratch, 0 = LDS
+    if (sw.dr_big >= 0) return sw.dr_big == 0;                                        // A/B switch for tests: 1 = global scratch, 0 = LDS
     return lds_bytes(h) * (size_t)min_waves <= 160 * 1024;
 }
 static void launch_init(mcmcx_engine *h)
 { hipLaunchKernelGGL(init_kernel, dim3(h->ntiles), dim3(64), 0, h->stream, h->E); }
-// ---- which sampling kernel runs: ONE table per launcher, walked in order -- the first entry whose predicate holds is launched and
-// its name noted for mcmcx_last_kernel (bench.py labels its roofline with it).  The tables are exported through
-// mcmcx_debug_kernel_table, so that tests/test_kernel_table.py can list every selectable instance and require a parity test that
-// asserted each of them.  A configuration no entry accepts is an error of the run (launch_err), never a silent no-launch.
+// ---- which sampling kernel runs: ONE table per launcher, walked in order by plan_kernels -- the first entry whose predicate holds is
+// the one the launcher runs, its name noted at each launch for mcmcx_last_kernel (bench.py labels its roofline with it).  The
+// predicates read the configuration and the plan only.  The tables are exported through mcmcx_debug_kernel_table, so that
+// tests/test_kernel_table.py can list every selectable instance and require a parity test that asserted each of them.  A configuration
+// no entry accepts is an error of the run (launch_err), never a silent no-launch.
 struct KernelEntry {
     const char *family;                                   // "step" (launch_step), "group" (launch_group), "scam" (launch_scam)
     const char *name;
     bool (*when)(const mcmcx_engine *);
     void (*launch)(mcmcx_engine *, int it0, int it1);
 };
-static void walk_table(mcmcx_engine *h, const KernelEntry *tab, size_t n, int it0, int it1)
+static const KernelEntry *pick_entry(const mcmcx_engine *h, const KernelEntry *tab, size_t n)
 {
     for (size_t i = 0; i < n; ++i)
-        if (tab[i].when(h)) { h->last_kernel = tab[i].name; tab[i].launch(h, it0, it1); return; }
-    h->launch_err = std::string("no ") + (n ? tab[0].family : "?") + " kernel covers this configuration";
+        if (tab[i].when(h)) return &tab[i];
+    return nullptr;
+}
+static void launch_entry(mcmcx_engine *h, const KernelEntry *e, const char *family, int it0, int it1)
+{
+    if (!e) { h->launch_err = std::string("no ") + family + " kernel covers this configuration"; return; }
+    h->last_kernel = e->name;
+    e->launch(h, it0, it1);
 }
 // ---- the lane-group step kernel (mcx_group.hpp): four chains per wave, factors in registers
 static const int GROUP_MAXSEG = 256;                  // iterations per launch (one accept byte per chain and iteration in d_accb)
@@ -146,7 +157,7 @@ template <int GW, int DRM>
 static void launch_group_d4(mcmcx_engine *h, int it0, int it1)
 {
     if constexpr (GW == 4) {                              // quads: npar <= 16
-        switch (h->group_d4) {
+        switch (h->plan.group_d4) {
         case 4: launch_group_tk<4, 4, DRM>(h, it0, it1); break;
         case 8: launch_group_tk<4, 8, DRM>(h, it0, it1); break;
         case 12: launch_group_tk<4, 12, DRM>(h, it0, it1); break;
@@ -154,7 +165,7 @@ static void launch_group_d4(mcmcx_engine *h, int it0, int it1)
         default: h->launch_err = "group kernel (quads): npar > 16";
         }
     } else {
-        switch (h->group_d4) {
+        switch (h->plan.group_d4) {
         case 4: launch_group_tk<16, 4, DRM>(h, it0, it1); break;
         case 8: launch_group_tk<16, 8, DRM>(h, it0, it1); break;
         case 12: launch_group_tk<16, 12, DRM>(h, it0, it1); break;
@@ -162,17 +173,17 @@ static void launch_group_d4(mcmcx_engine *h, int it0, int it1)
         case 20: launch_group_tk<16, 20, DRM>(h, it0, it1); break;
         case 24: launch_group_tk<16, 24, DRM>(h, it0, it1); break;
         default:
-            // DRM = 2 (iC as a square in LDS) is the engine's choice up to npar 24 only (mcmcx_init): larger sizes are not instantiated --
+            // DRM = 2 (iC as a square in LDS) is the plan's choice up to npar 24 only (plan_kernels): larger sizes are not instantiated --
             // at 28 / 32 they could not hold the two waves per SIMD they would declare (Weak 12)
             if constexpr (DRM != 2) {
-                switch (h->group_d4) {
+                switch (h->plan.group_d4) {
                 case 28: launch_group_tk<16, 28, DRM>(h, it0, it1); return;
                 case 32: launch_group_tk<16, 32, DRM>(h, it0, it1); return;
                 default: break;
                 }
             }
             if constexpr (DRM == 0) {                                    // (above 32: sizes of eight, no delayed rejection)
-                switch (h->group_d4) {
+                switch (h->plan.group_d4) {
                 case 40: launch_group_tk<16, 40, DRM>(h, it0, it1); return;
                 case 48: launch_group_tk<16, 48, DRM>(h, it0, it1); return;
                 case 56: launch_group_tk<16, 56, DRM>(h, it0, it1); return;
@@ -186,27 +197,27 @@ static void launch_group_d4(mcmcx_engine *h, int it0, int it1)
     }
 }
 static const KernelEntry GROUP_TABLE[] = {
-    {"group", "group_step_kernel",            [](const mcmcx_engine *h) { return h->group_gw == 16 && h->group_drm == 0; },
+    {"group", "group_step_kernel",            [](const mcmcx_engine *h) { return h->plan.group_gw == 16 && h->plan.group_drm == 0; },
         launch_group_d4<16, 0>},
-    {"group", "group_step_kernel<DR>",        [](const mcmcx_engine *h) { return h->group_gw == 16 && h->group_drm == 1; },
+    {"group", "group_step_kernel<DR>",        [](const mcmcx_engine *h) { return h->plan.group_gw == 16 && h->plan.group_drm == 1; },
         launch_group_d4<16, 1>},
-    {"group", "group_step_kernel<DR2>",       [](const mcmcx_engine *h) { return h->group_gw == 16 && h->group_drm == 2; },
+    {"group", "group_step_kernel<DR2>",       [](const mcmcx_engine *h) { return h->plan.group_gw == 16 && h->plan.group_drm == 2; },
         launch_group_d4<16, 2>},
-    {"group", "group_step_kernel<quad>",      [](const mcmcx_engine *h) { return h->group_gw == 4 && h->group_drm == 0; },
+    {"group", "group_step_kernel<quad>",      [](const mcmcx_engine *h) { return h->plan.group_gw == 4 && h->plan.group_drm == 0; },
         launch_group_d4<4, 0>},
-    {"group", "group_step_kernel<quad, DR>",  [](const mcmcx_engine *h) { return h->group_gw == 4 && h->group_drm == 1; },
+    {"group", "group_step_kernel<quad, DR>",  [](const mcmcx_engine *h) { return h->plan.group_gw == 4 && h->plan.group_drm == 1; },
         launch_group_d4<4, 1>},
-    {"group", "group_step_kernel<quad, DR2>", [](const mcmcx_engine *h) { return h->group_gw == 4 && h->group_drm == 2; },
+    {"group", "group_step_kernel<quad, DR2>", [](const mcmcx_engine *h) { return h->plan.group_gw == 4 && h->plan.group_drm == 2; },
         launch_group_d4<4, 2>},
 };
 static void launch_group(mcmcx_engine *h, int it0, int it1)
 {
-    if (h->group_drm == 2 && h->group_check_due) {       // the factors have been rewritten since the last look
+    if (h->plan.group_drm == 2 && h->group_check_due) {  // the factors have been rewritten since the last look
         (void)hipMemsetAsync(h->d_gflag, 0, sizeof(int), h->stream);
         hipLaunchKernelGGL(group_check_kernel, dim3(h->ntiles), dim3(64), 0, h->stream, h->E, h->d_gflag);
         h->group_check_due = false;
     }
-    walk_table(h, GROUP_TABLE, sizeof(GROUP_TABLE) / sizeof(GROUP_TABLE[0]), it0, it1);
+    launch_entry(h, h->plan.step, "group", it0, it1);
     if (h->d_accb && h->launch_err.empty()) {
         const long long n = (long long)(it1 - it0 + 1) * h->ntiles;
         hipLaunchKernelGGL(group_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->E, h->d_accb, it0, it1);
@@ -215,10 +226,10 @@ static void launch_group(mcmcx_engine *h, int it0, int it1)
 // pooled_mfma_kernel<false, true>: two waves per SIMD (256 registers, some state spilled) pay with more tiles than SIMDs: from two per SIMD
 // where the LDS vector lets eight waves on a CU (npar <= 39: +25 .. +55 %), from eight where it lets six (npar 50: 0.80 at 2048 tiles, 0.99
 // at 4096, 1.14 at 16384); with one tile per SIMD the spills are all they buy (0.83 .. 0.90) -- tools/pooled_waves_probe.py
-static bool pooled_two_waves(const mcmcx_engine *h)
+static bool pooled_two_waves(const mcmcx_engine *h, const mcx_switches &sw)
 {
     // (test switch: either instance on a small problem)
-    if (h->sw.pooled_waves == 1 || h->sw.pooled_waves == 2) return h->sw.pooled_waves == 2;
+    if (sw.pooled_waves == 1 || sw.pooled_waves == 2) return sw.pooled_waves == 2;
     return h->ntiles >= (pooled_mfma_lds(h->d) * 8 <= 160 * 1024 ? 2048 : 8192);
 }
 // pooled_mfma_ks_kernel: the forty-row LDS vector (eight tiles on a CU whatever npar is) where the whole vector leaves fewer, for the
@@ -227,13 +238,13 @@ static bool pooled_two_waves(const mcmcx_engine *h)
 // 1.12 .. 1.25 at 53..64 (five); with a non-Gaussian target 1.05 .. 1.42.  Against what the engine took before at fewer tiles
 // (tools/pooled_ks_tiles.py; pooled_mfma_kernel<false> below 8192): 1.15 .. 1.22 at 2048 / 4096 tiles for npar 45 / 50, 0.98 / 1.02 at 64;
 // 0.63 .. 0.69 at 1024 tiles (one per SIMD: the spills are all two waves buy there).
-static bool pooled_forty_rows(const mcmcx_engine *h)
+static bool pooled_forty_rows(const mcmcx_engine *h, const mcx_switches &sw)
 {
     const int d4 = (h->d + 3) & ~3;
-    if (!pooled_use_mfma(h) || h->dodr || d4 <= PKS || d4 > 64) return false;
+    if (!pooled_use_mfma(h, sw) || h->dodr || d4 <= PKS || d4 > 64) return false;
     // (test switch: either form on a small problem)
-    if (h->sw.pooled_ks == 0 || h->sw.pooled_ks == 1) return h->sw.pooled_ks == 1;
-    return h->sw.pooled_waves != 1 && h->ntiles >= 2048;
+    if (sw.pooled_ks == 0 || sw.pooled_ks == 1) return sw.pooled_ks == 1;
+    return sw.pooled_waves != 1 && h->ntiles >= 2048;
 }
 #define STEP_ARGS h->stream, h->E, it0, it1
 #define STEP_RS (h->d_ramscale + it0)
@@ -262,7 +273,7 @@ static void launch_group_ram_d4(mcmcx_engine *h, int it0, int it1)
 }
 static void launch_group_ram(mcmcx_engine *h, int it0, int it1)
 {
-    switch (h->ram_group_d4) {
+    switch (h->plan.ram_group_d4) {
     case 16: launch_group_ram_d4<16>(h, it0, it1); break;
     case 32: launch_group_ram_d4<32>(h, it0, it1); break;
     case 56: launch_group_ram_d4<56>(h, it0, it1); break;
@@ -284,31 +295,32 @@ static void launch_group_ram(mcmcx_engine *h, int it0, int it1)
 static const KernelEntry STEP_TABLE[] = {
     // ---- a device target with response columns (nycol >= 1 sums of squares per point): the phases of an iteration in one launch
     // (one instantiation per method class: MCMC_run_ram's carries the rank-one update's panels, the others do not)
-    {"step", "step_kernel_cols<ram>", [](const mcmcx_engine *h) { return fused_cols(h) && h->E.method == M_RAM; },
+    {"step", "step_kernel_cols<ram>", [](const mcmcx_engine *h) { return h->plan.fused_cols && kernel_method(h) == M_RAM; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<1>, G1, lds_step(h), STEP_ARGS,
          (const double *)h->d_ramscale, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
-    {"step", "step_kernel_cols", fused_cols,
+    {"step", "step_kernel_cols", [](const mcmcx_engine *h) { return h->plan.fused_cols; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<0>, G1, lds_step(h), STEP_ARGS,
          (const double *)h->d_ramscale, (const double *)(h->pooled ? h->E.sharedR : nullptr), (const double *)h->d_sharedR2,
          (const double *)h->d_sharediC); }},
     // ---- pooled mode (one shared factor)
-    {"step", "pooled_mfma_kernel<true>", [](const mcmcx_engine *h) { return pooled_use_mfma(h) && h->dodr != 0; },
+    {"step", "pooled_mfma_kernel<true>", [](const mcmcx_engine *h) { return h->plan.pooled_dr_mfma; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<true>, G1, pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT,
          h->d_sharedRT, h->d_sharedR2T, h->d_sharediCd); }},
     MCX_VARIANT_STEP_ENTRIES
-    {"step", "pooled_mfma_ks_kernel", pooled_forty_rows,
+    {"step", "pooled_mfma_ks_kernel", [](const mcmcx_engine *h) { return h->plan.pooled_forty_rows; },
      [](mcmcx_engine *h, int it0, int it1) {
          // (npar 49..52: the fourth output block has four rows and goes through the 4 x 4 x 4 instruction)
          const size_t lds = (size_t)PKS * 64 * sizeof(double);
          if (((h->d + 3) & ~3) == 52) hipLaunchKernelGGL(pooled_mfma_ks_kernel<true>, G1, lds, STEP_ARGS, STEP_TGT, h->d_sharedRT);
          else hipLaunchKernelGGL(pooled_mfma_ks_kernel<false>, G1, lds, STEP_ARGS, STEP_TGT, h->d_sharedRT); }},
-    {"step", "pooled_mfma_kernel<false, true>", [](const mcmcx_engine *h) { return pooled_use_mfma(h) && pooled_two_waves(h); },
+    {"step", "pooled_mfma_kernel<false, true>", [](const mcmcx_engine *h) {
+        return h->plan.pooled_mfma && h->plan.pooled_two_waves; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((pooled_mfma_kernel<false, true>), G1, pooled_mfma_lds(h->d), STEP_ARGS,
          STEP_TGT, h->d_sharedRT, (const double *)nullptr, (const double *)nullptr); }},
-    {"step", "pooled_mfma_kernel<false>", [](const mcmcx_engine *h) { return pooled_use_mfma(h); },
+    {"step", "pooled_mfma_kernel<false>", [](const mcmcx_engine *h) { return h->plan.pooled_mfma; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<false>, G1, pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT,
          h->d_sharedRT, (const double *)nullptr, (const double *)nullptr); }},
-    {"step", "step_kernel_pooled_dr_big", [](const mcmcx_engine *h) { return h->pooled && h->dodr && !dr_vectors_in_lds(h, 4); },
+    {"step", "step_kernel_pooled_dr_big", [](const mcmcx_engine *h) { return h->pooled && h->dodr && !h->plan.dr_vectors_in_lds; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_pooled_dr_big, G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
          h->E.sharedR, h->d_sharedR2, h->d_sharediC); }},
     {"step", "step_kernel_pooled_dr", [](const mcmcx_engine *h) { return h->pooled && h->dodr; },
@@ -318,30 +330,31 @@ static const KernelEntry STEP_TABLE[] = {
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<false, false, true>), G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
          h->E.sharedR); }},
     // ---- method = 'ram', per-chain factors
-    {"step", "group_ram_kernel", [](const mcmcx_engine *h) { return h->ram_group_d4 != 0; }, launch_group_ram},
-    {"step", "step_kernel_ram_fullr", [](const mcmcx_engine *h) { return h->E.method == M_RAM && h->usesvd; },
+    {"step", "group_ram_kernel", [](const mcmcx_engine *h) { return h->plan.ram_group_d4 != 0; }, launch_group_ram},
+    {"step", "step_kernel_ram_fullr", [](const mcmcx_engine *h) { return kernel_method(h) == M_RAM && h->usesvd; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ram_fullr, G1, 0, STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR);
          }},
-    {"step", "step_kernel_ram_ldsr", [](const mcmcx_engine *h) { return h->E.method == M_RAM && h->E.lds_scratch == 3; },
+    {"step", "step_kernel_ram_ldsr", [](const mcmcx_engine *h) {
+        return kernel_method(h) == M_RAM && h->plan.lds_form == LDS_RAM_R; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ram_ldsr, G1, (size_t)(2 * h->d + h->P) * 64 * sizeof(double),
          STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel_ram_wide", [](const mcmcx_engine *h) {
-        return h->E.method == M_RAM && h->d > RAM_SMALL_MAX && h->sw.ram_wide != 0; },
+        return kernel_method(h) == M_RAM && h->d > RAM_SMALL_MAX && h->plan.ram_wide; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ram_wide, G1, (size_t)NLC * 2 * 64 * sizeof(double), STEP_ARGS,
          STEP_RS, STEP_TGT, h->E.sharedR); }},
-    {"step", "step_kernel<true, false, false>", [](const mcmcx_engine *h) { return h->E.method == M_RAM; },
+    {"step", "step_kernel<true, false, false>", [](const mcmcx_engine *h) { return kernel_method(h) == M_RAM; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<true, false, false>), G1,
          (size_t)NLC * 2 * 64 * sizeof(double), STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
     // ---- delayed rejection, per-chain factors: the second stage's two vectors in global scratch / in LDS
-    {"step", "step_kernel_dr_big", [](const mcmcx_engine *h) { return h->dodr && !dr_vectors_in_lds(h); },
+    {"step", "step_kernel_dr_big", [](const mcmcx_engine *h) { return h->dodr && !h->plan.dr_vectors_in_lds; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_dr_big, G1, 0, STEP_ARGS, STEP_TGT); }},
     {"step", "step_kernel_dr", [](const mcmcx_engine *h) { return h->dodr != 0; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_dr, G1, lds_step(h), STEP_ARGS, STEP_TGT); }},
     // ---- AM / Metropolis / early rejection: state + factor in LDS, state in LDS, nothing in LDS
-    {"step", "step_kernel_ldsr", [](const mcmcx_engine *h) { return h->E.lds_scratch == 2; },
+    {"step", "step_kernel_ldsr", [](const mcmcx_engine *h) { return h->plan.lds_form == LDS_STATE_R; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ldsr, G1, (size_t)(2 * h->d + h->P) * 64 * sizeof(double),
          STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
-    {"step", "step_kernel_ldsv", [](const mcmcx_engine *h) { return h->E.lds_scratch != 0; },
+    {"step", "step_kernel_ldsv", [](const mcmcx_engine *h) { return h->plan.lds_form != LDS_NONE; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ldsv, G1, (size_t)4 * h->d * 64 * sizeof(double), STEP_ARGS,
          STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel<false, false, false>", [](const mcmcx_engine *) { return true; },
@@ -350,8 +363,8 @@ static const KernelEntry STEP_TABLE[] = {
 };
 static void launch_step(mcmcx_engine *h, int it0, int it1)
 {
-    if (h->group_d4) { launch_group(h, it0, it1); return; }
-    walk_table(h, STEP_TABLE, sizeof(STEP_TABLE) / sizeof(STEP_TABLE[0]), it0, it1);
+    if (h->plan.group_d4) launch_group(h, it0, it1);
+    else launch_entry(h, h->plan.step, "step", it0, it1);
 }
 // every chain's copy of a K-vector, filled on the device
 static int dev_bcast(mcmcx_engine *h, double *dst, const std::vector<double> &v)
@@ -394,7 +407,7 @@ static size_t scam_pooled_lds(int d) {
     return ((size_t)((d + 15) / 16) * (16 + 4) * 64 + 128 + (size_t)((d + 15) / 16) * 16) * sizeof(double); }
 static int upload_shared_u(mcmcx_engine *h)
 {
-    if (h->scam_replicated) {                           // every chain's own copy of the one rotation and its scales
+    if (h->plan.scam_replicated) {                           // every chain's own copy of the one rotation and its scales
         int rc = dev_bcast(h, h->E.Rf, h->pool_U); if (rc) return rc;
         return dev_bcast(h, h->E.qstd, h->pool_std);
     }
@@ -408,66 +421,161 @@ static int upload_shared_u(mcmcx_engine *h)
     return 0;
 }
 // 13..15 output blocks (npar 193..240): twelve waves of 170 registers (scam_pooled12_kernel) instead of sixteen of 128
-static bool scam_use_12(const mcmcx_engine *h)
+static bool scam_use_12(const mcmcx_engine *h, const mcx_switches &sw)
 {
     const int nt = (h->d + 15) / 16;
-    if (h->sw.scam_pooled_16 > 0) return false;                                       // A/B switch for tests: the sixteen-wave layout
+    if (sw.scam_pooled_16 > 0) return false;                                          // A/B switch for tests: the sixteen-wave layout
     return nt >= 13 && nt <= 15;
 }
 // opt-in fast proposals with the Gaussian target: the workgroup-per-tile kernel of the pooled mode with each chain's own
 // rotation column (g_U = nullptr) -- the target's d x d product on the matrix cores instead of lane by lane
-static bool scam_fast_tile_kernel(const mcmcx_engine *h)
+static bool scam_fast_tile_kernel(const mcmcx_engine *h, const mcx_switches &sw)
 {
     return h->cfg.scam_fast && h->tkind == TGT_GAUSS && !h->has_lo && !h->has_hi && !h->has_pri && scam_pooled_lds(h->d) <= 160 * 1024 &&
-           !(h->sw.scam_fast_lanes > 0);
+           !(sw.scam_fast_lanes > 0);
 }
 // few tiles: several waves per tile (scam_mw_kernel), so that a sub-step is not bound by the latency of one wave's loads
 // while most of the chip idles -- as many waves as keep the chip's ~2048 resident-wave slots busy, at most 8 (sixteen
 // waves of 128 registers spill the products' panels)
 static size_t scam_mw_lds(const mcmcx_engine *h) { return (size_t)(4 * ((h->d + 15) / 16) + 2) * 64 * sizeof(double); }
-static int scam_tile_waves(const mcmcx_engine *h)
+static int scam_tile_waves(const mcmcx_engine *h, const mcx_switches &sw)
 {
     int nw = 1;
     // (1024 tiles x npar 200: 8.4e6 at two waves per tile, 8.9e6 at four, 9.0e6 at eight -- profiles/r05_d/c5rep_waves.txt)
     while (nw < 8 && (long long)h->ntiles * nw * 2 <= 8192) nw *= 2;
-    { const int v = h->sw.scam_waves; if (v == 1 || v == 2 || v == 4 || v == 8) nw = v; }   // A/B switch for tests
+    { const int v = sw.scam_waves; if (v == 1 || v == 2 || v == 4 || v == 8) nw = v; }   // A/B switch for tests
     // (npar > 1200: the one-wave kernel needs no LDS)
     if (scam_mw_lds(h) > 160 * 1024) nw = 1;
     return nw;
 }
 #define SCAM_POOLED_ARGS scam_pooled_lds(h->d), h->stream, h->E, it0, it1, h->E.tgt.mu, h->E.tgt.lamT
 static const KernelEntry SCAM_TABLE[] = {
-    {"scam", "step_kernel_cols<scam>", [](const mcmcx_engine *h) { return fused_cols(h) && !h->pooled; },
+    {"scam", "step_kernel_cols<scam>", [](const mcmcx_engine *h) { return h->plan.fused_cols && !h->pooled; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<2>, G1, 0, STEP_ARGS, (const double *)h->d_ramscale,
          (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
     // pooled: 16-row output blocks, min(12, 4*(nt/4)) block waves + 4 chain-group waves; twelve waves of 170 registers for 13..15 blocks
-    {"scam", "scam_pooled12_kernel", [](const mcmcx_engine *h) { return h->pooled && !h->scam_replicated && scam_use_12(h); },
+    {"scam", "scam_pooled12_kernel", [](const mcmcx_engine *h) { return h->pooled && !h->plan.scam_replicated && h->plan.scam_pooled12; },
      [](mcmcx_engine *h, int it0, int it1) { const size_t st = shared_u_stride(h);
         hipLaunchKernelGGL(scam_pooled12_kernel, dim3(h->ntiles), dim3(768), SCAM_POOLED_ARGS, h->d_sharedU, h->d_sharedU + st,
             h->d_sharedU + 2 * st); }},
-    {"scam", "scam_pooled_kernel", [](const mcmcx_engine *h) { return h->pooled && !h->scam_replicated; },
+    {"scam", "scam_pooled_kernel", [](const mcmcx_engine *h) { return h->pooled && !h->plan.scam_replicated; },
      [](mcmcx_engine *h, int it0, int it1) { const size_t st = shared_u_stride(h); const int nw = 4 + std::min(12, ((h->d + 15) / 16) & ~3);
         hipLaunchKernelGGL(scam_pooled_kernel, dim3(h->ntiles), dim3(64 * nw), SCAM_POOLED_ARGS, h->d_sharedU, h->d_sharedU + st,
             h->d_sharedU + 2 * st); }},
     // (the sixteen-wave layout whatever npar: every lane fetches the column of its own chain's factor per sub-step, and four
     //  waves per SIMD cover that better than three -- 4.62e8 against 4.45e8 proposals/s at npar 200)
-    {"scam", "scam_pooled_kernel<per-chain>", scam_fast_tile_kernel,
+    {"scam", "scam_pooled_kernel<per-chain>", [](const mcmcx_engine *h) { return h->plan.scam_fast_tile; },
      [](mcmcx_engine *h, int it0, int it1) { const int nw = 4 + std::min(12, ((h->d + 15) / 16) & ~3);
         hipLaunchKernelGGL(scam_pooled_kernel, dim3(h->ntiles), dim3(64 * nw), SCAM_POOLED_ARGS, (const double *)nullptr,
             (const double *)nullptr, (const double *)nullptr); }},
-    {"scam", "scam_mw_kernel<8>", [](const mcmcx_engine *h) { return scam_tile_waves(h) == 8; },
+    {"scam", "scam_mw_kernel<8>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 8; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<8>, dim3(h->ntiles), dim3(512), scam_mw_lds(h), STEP_ARGS,
          STEP_TGT); }},
-    {"scam", "scam_mw_kernel<4>", [](const mcmcx_engine *h) { return scam_tile_waves(h) == 4; },
+    {"scam", "scam_mw_kernel<4>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 4; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<4>, dim3(h->ntiles), dim3(256), scam_mw_lds(h), STEP_ARGS,
          STEP_TGT); }},
-    {"scam", "scam_mw_kernel<2>", [](const mcmcx_engine *h) { return scam_tile_waves(h) == 2; },
+    {"scam", "scam_mw_kernel<2>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 2; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<2>, dim3(h->ntiles), dim3(128), scam_mw_lds(h), STEP_ARGS,
          STEP_TGT); }},
     {"scam", "scam_kernel", [](const mcmcx_engine *) { return true; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_kernel, G1, 0, STEP_ARGS, STEP_TGT); }},
 };
-static void launch_scam(mcmcx_engine *h, int it0, int it1)
+static void launch_scam(mcmcx_engine *h, int it0, int it1) { launch_entry(h, h->plan.scam, "scam", it0, it1); }
+// the adaptation's SVD one workgroup per chain (mcx_svd.hpp) where its rings and row groups are instantiated
+static bool svd_blocked(const mcmcx_engine *h, const mcx_switches &sw)
 {
-    walk_table(h, SCAM_TABLE, sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]), it0, it1);
+    if (!h->usesvd || h->pooled || h->cfg.method == MCMCX_METHOD_RAM) return false;
+    // test switch: the lane SVD (the engine's form below npar 48 and above 256)
+    if (sw.svd_lane > 0) return false;
+    // (its rings and row groups are instantiated up to npar 256)
+    return h->d >= 48 && h->d <= 256;
+}
+// ---- the plan: every kernel form the engine takes, decided once at mcmcx_init before anything is allocated.  Its inputs are the
+// configuration, the problem's shape, the target kind, the switches (read here, nowhere else) and the CU count; never a device pointer.
+static void plan_kernels(mcmcx_engine *h)
+{
+    mcx_switches sw;
+    sw.read();                                       // the A/B switches as the environment has them now: fixed for the engine's life
+    KernelPlan &p = h->plan;
+    p = KernelPlan();
+    const mcmcx_config &c = h->cfg;
+    const int d = h->d, P = h->P, T = h->ntiles;
+    const bool am = (c.method != MCMCX_METHOD_RAM) && (c.doadapt != 0 || c.doburnin != 0) && !h->pooled;
+    p.dr_lds = h->dodr && dr_fits_lds(h);
+    p.dr_vectors_in_lds = dr_vectors_in_lds(h, sw, h->pooled ? 4 : 8);
+    {   // plain AM / Metropolis / ER step kernel: state and scratch vectors in LDS (4 d x 512 bytes per wave) when that costs no
+        // occupancy -- eight waves per CU still fit (npar <= 10), or all tiles are resident at once anyway (few chains)
+        const size_t per_wave = (size_t)4 * d * 64 * sizeof(double);
+        const int per_cu = (int)((size_t)160 * 1024 / per_wave);
+        hipDeviceProp_t prop;
+        int cus = 256;
+        if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+        const bool fits = per_cu >= 8 || (per_cu >= 1 && (long long)T <= (long long)per_cu * cus);
+        // (MCMCX_LDS_SCRATCH = 0: off, A/B)
+        p.lds_form = (!h->pooled && !h->dodr && c.method != MCMCX_METHOD_RAM && c.method != MCMCX_METHOD_SCAM && fits
+            && sw.lds_scratch != 0) ? LDS_STATE : LDS_NONE;
+        // ... and the packed factor with it (step_kernel_ldsr) where one column panel covers npar and state + factor of all tiles
+        // are resident at once: (2 npar + npar (npar + 1) / 2) x 512 bytes per wave, 38 KiB at npar = 10 = four waves per CU
+        const size_t per_wave_r = (size_t)(2 * d + P) * 64 * sizeof(double);
+        const int per_cu_r = (int)((size_t)160 * 1024 / per_wave_r);
+        const bool fits_r = per_cu_r >= 8 || (per_cu_r >= 1 && (long long)T <= (long long)per_cu_r * cus);
+        // MCMCX_LDS_SCRATCH=1: the state only (A/B)
+        if (p.lds_form != LDS_NONE && !h->usesvd && d <= TW && fits_r && sw.lds_scratch != 1) p.lds_form = LDS_STATE_R;
+        // method='ram' (per-chain factor, Cholesky form): the factor DCHUD / DCHDD rewrite every iteration, and their rotations, in LDS for
+        // the launch where one column panel covers npar and all tiles are resident at once (step_kernel_ram_ldsr)
+        if (!h->pooled && c.method == MCMCX_METHOD_RAM && !h->usesvd && d <= RW && fits_r && sw.lds_scratch != 0) p.lds_form = LDS_RAM_R;
+    }
+    // the user's functions on the host and at most sixteen tiles: candidate, results and flags in mapped host memory -- a phase kernel's
+    // stores ARE the hand-over, the host's results are read by the next one in place (MCMCX_HOST_MAPPED=0: device buffers and copies)
+    p.host_mapped = h->tkind == TGT_HOST && T <= 16 && sw.host_mapped != 0;
+    // (RAM / SCAM use cs as sweep scratch)
+    p.cs_mapped = p.host_mapped && (c.method == MCMCX_METHOD_DRAM || c.method == MCMCX_METHOD_ER);
+    // (MCMCX_HOST_FUSE=0: one launch per phase, the A/B form the tests compare with)
+    p.host_fuse = sw.host_fuse != 0;
+    // the response-column target: the phases fused into one launch per segment (step_kernel_cols); MCMCX_COLS_PHASED=1 keeps the
+    // separate launches (A/B, tests)
+    p.fused_cols = h->tkind == TGT_EXPCOLS && !(sw.cols_phased > 0);
+    // pooled SCAM: npar > 240: slower, not refused -- scam_kernel / scam_mw_kernel on per-chain copies
+    p.scam_replicated = h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM && scam_pooled_lds(d) > 160 * 1024;
+    p.pooled_mfma = pooled_use_mfma(h, sw);
+    p.pooled_dr_mfma = p.pooled_mfma && h->dodr;                 // the second stage on the matrix cores too
+    p.pooled_two_waves = pooled_two_waves(h, sw);
+    p.pooled_forty_rows = pooled_forty_rows(h, sw);
+    p.ram_wide = sw.ram_wide != 0;
+    p.scam_pooled12 = scam_use_12(h, sw);
+    p.scam_fast_tile = scam_fast_tile_kernel(h, sw);
+    p.scam_waves = scam_tile_waves(h, sw);
+    // the lane-group step kernel where it covers the configuration: MCMCX_GROUP = 1 / 0 forces it on / off (A/B, tests)
+    if (group_covers(h)) {
+        int ex = 0;
+        const bool pow2 = h->dodr && c.drscale > 0.0 && std::frexp(c.drscale, &ex) == 0.5 && ex > -64 && ex < 64;
+        // (the power-of-two form keeps iC in LDS: above npar 24 that leaves fewer waves per CU than the register form's four)
+        const int drm = !h->dodr ? 0 : (pow2 && d <= 24 && sw.group_dr2 != 0) ? 2 : 1;
+        // (MCMCX_GROUP_GW 4 / 16: A/B, tests)
+        const int gw = (d <= 16 && sw.group_gw != -1) ? (sw.group_gw == 4 ? 4 : 16) : group_width(h);
+        if (sw.group != -1 ? sw.group != 0 : group_wins(h, drm, gw)) {
+            p.group_d4 = d <= 32 ? ((d + 3) & ~3) : ((d + 7) & ~7);
+            p.group_gw = gw;
+            p.group_drm = drm;
+        }
+    }
+    // method = 'ram' with few chains on the lane-group kernel (MCMCX_RAM_GROUP = 1 / 0: always where it covers / never; A/B, tests)
+    if (ram_group_covers(h)) {
+        const int rg = sw.ram_group != -1 ? sw.ram_group : sw.group;  // (the kernel-family switch of the tests covers it too)
+        if (rg != -1 ? rg != 0 : ram_group_wins(h)) p.ram_group_d4 = d <= 16 ? 16 : d <= 32 ? 32 : d <= 56 ? 56 : 64;
+    }
+    // the adaptation's factorisation (Cholesky branch) with the matrices in LDS (tile_factor_kernel): any chain count, npar <= 32 -- config
+    // 3's size (npar 20, delayed rejection, 262144 chains): 2.11 -> 1.44 ms per tick, bound by VALU issue (~25 instructions per inner step
+    // of four chains). Above npar 32 adapt_post_kernel's 8 x 8 register blocks stay: at npar 50 x 1 048 576 chains they stream the matrices
+    // ~5.6 times (16.0 ms) and still beat the LDS form, whose three waves per CU issue ~15 x the instructions per chain (35.2 ms;
+    // profiles/r05_a/tick_ab.txt). MCMCX_TILE_FACTOR = 0 / 1: never / up to npar 64 (test switch: both forms on one problem).
+    p.tile_factor = am && !h->usesvd && d <= (sw.tile_factor == 1 ? 64 : 32) && sw.tile_factor != 0;
+    // (an adaptation that never runs needs no form)
+    p.svd_blocked = svd_blocked(h, sw) && (c.doadapt != 0 || c.doburnin != 0);
+    // (test switch: covmat_rows, the lane form)
+    p.cov_batch = !(sw.cov_batch_rows > 0);
+    // every predicate's inputs are fixed from here on: the launchers run the entry found now
+    if (c.method == MCMCX_METHOD_SCAM) p.scam = pick_entry(h, SCAM_TABLE, sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]));
+    else if (p.group_d4) p.step = pick_entry(h, GROUP_TABLE, sizeof(GROUP_TABLE) / sizeof(GROUP_TABLE[0]));
+    else p.step = pick_entry(h, STEP_TABLE, sizeof(STEP_TABLE) / sizeof(STEP_TABLE[0]));
 }

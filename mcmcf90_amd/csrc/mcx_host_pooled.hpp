@@ -136,7 +136,7 @@ static int pooled_upload_dr(mcmcx_engine *h, bool fresh)
     HIPCHK(hipMemcpyAsync(h->d_sharediC, h->pool_iC.data(), (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     // pooled_mfma_kernel<true>: R2 like d_sharedRT (M[s*d + o] = R2(s,o)), iC dense symmetric
-    if (h->d_sharedR2T) {
+    if (h->plan.pooled_dr_mfma) {
         const int d4 = (d + 3) & ~3;
         std::vector<double> m((size_t)d4 * d + PWS, 0.0), q((size_t)d4 * d + PWS, 0.0);
         // the full factor as it stands: M[s*d + o] = R2f(o, s)

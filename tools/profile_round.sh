@@ -6,17 +6,28 @@
 #   write/  rocprofv3 --pmc WRITE_SIZE        (own pass)              -> HBM write bytes per launch
 #   sq/     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES
 #   grbm/   rocprofv3 --pmc GRBM_GUI_ACTIVE                           -> effective clock
+# Each pass runs under its own time limit (PASS_SECONDS, default 300); the first pass that exits non-zero ends the script with its
+# status and is named on stderr -- no GPU program starts after one has failed.
 # Summaries: python tools/profile_summary.py gpurun_out/prof/TAG
 TAG=$1; shift
 REPO=$PWD
 OUT=$REPO/gpurun_out/prof/$TAG
+LIMIT=${PASS_SECONDS:-300}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $REPO/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs "$@" > $OUT/bench_kt.json 2> $OUT/kt.err
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs "$@" > $OUT/bench_fetch.json 2> $OUT/fetch.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs "$@" > $OUT/bench_write.json 2> $OUT/write.err
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES --output-format csv -d $OUT/sq -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs "$@" > $OUT/bench_sq.json 2> $OUT/sq.err
-rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $OUT/grbm -o pmc -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs "$@" > $OUT/bench_grbm.json 2> $OUT/grbm.err
+pass() {   # pass NAME STEPS WARMUP rocprofv3-arguments...
+    local name=$1 steps=$2 warmup=$3; shift 3
+    timeout -k 10 $LIMIT rocprofv3 "$@" --output-format csv -d $OUT/$name -- python3 $REPO/bench.py --steps $steps --warmup $warmup \
+        --no-cpu-baseline --no-other-configs "${ARGS[@]}" > $OUT/bench_$name.json 2> $OUT/$name.err
+    local rc=$?
+    if [ $rc -ne 0 ]; then echo "profile_round.sh $TAG: pass $name exited with status $rc (see $OUT/$name.err)" >&2; exit $rc; fi
+}
+ARGS=("$@")
+pass kt 8 2 --kernel-trace --stats -o kt
+pass fetch 3 1 --pmc FETCH_SIZE -o pmc
+pass write 3 1 --pmc WRITE_SIZE -o pmc
+pass sq 3 1 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES -o pmc
+pass grbm 3 1 --pmc GRBM_GUI_ACTIVE -o pmc
 cd $REPO
 python3 tools/profile_summary.py $OUT > $OUT/summary.json 2> $OUT/summary.err
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
