@@ -6,7 +6,8 @@
 // form.  No CPU fallback: every numerical step of the sampler runs in the HIP kernels
 // of mcx_kernels.hpp; without a GPU every entry point that needs one fails.
 // ONE translation unit: the host parts below are included in order (engine object, initial factor, kernel selection and
-// launchers, adaptation tick, pooled mode and communicator, host callbacks); this file holds the extern "C" entry points.
+// launchers, adaptation tick, pooled mode and communicator, host callbacks); this file holds the extern "C" entry points and
+// mcmcx_init's steps.
 #include <hip/hip_runtime.h>
 #include <csignal>
 #include <cmath>
@@ -291,13 +292,13 @@ int mcmcx_set_priors(mcmcx_handle h, const double *mu, const double *sig)
     return 0;
 }
 
-int mcmcx_init(mcmcx_handle h)
+// ---- mcmcx_init in steps.  What needs no device memory comes first, so that an invalid configuration allocates nothing; where one
+// trips several checks the code that wins is, in this order: -30, -36, -31 (init_check), then -- the plan made -- the pooled -36, -32,
+// the two pooled -8, -34 and the external-target -8 (initial_factor).
+struct InitialFactor { std::vector<double> Rp, Cp, Rfull, qstd, iCp, R2p; };  // R(cmat0), cmat0 packed; the SVD factor; DR: dpotri(R), R2
+static int init_check(mcmcx_engine *h)
 {
-    if (!h) return fail(-1, "null handle");
-    if (h->inited) return fail(1, "Warning(mcmcinit): allready inited");            // MCMC_init.F90:24-27
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const mcmcx_config &c = h->cfg;
-    const int d = h->d, P = h->P, T = h->ntiles;
+    const int d = h->d;
     if ((int)h->par0.size() != d) return fail(-30, "user initialization error: par0 not set");
     if (h->cmat0.empty()) {                                                           // MCMC_initcmat0: identity
         h->cmat0.assign((size_t)d * d, 0.0);
@@ -314,39 +315,55 @@ int mcmcx_init(mcmcx_handle h)
     if (h->tkind == TGT_EXPCOLS
         && h->tncols != ny) return fail(-36, "response-column target: mcmcx_set_sigma2nobs must give one sigma2 / nobs per column");
     if (h->tkind < 0) return fail(-31, "no target: the device engine needs mcmcx_set_target_*");
-    plan_kernels(h);                                 // which kernels run: decided here, once; what follows allocates as the plan says
-    if (ny > 1 && h->pooled && (!h->plan.fused_cols || c.method == MCMCX_METHOD_SCAM))
+    return 0;
+}
+static int initial_factor(mcmcx_engine *h, InitialFactor &f)
+{
+    const mcmcx_config &c = h->cfg;
+    const int d = h->d, P = h->P;
+    if (h->ny > 1 && h->pooled && (!h->plan.fused_cols || c.method == MCMCX_METHOD_SCAM))
         return fail(-36, "nycol > 1 in pooled mode: the device-resident response-column target only, and not with method = 'scam'");
-    std::vector<double> Rp, Cp, Rfull, qstd0;
-    int info = host_initial_R(d, h->cmat0, Rp, Cp);
+    int info = host_initial_R(d, h->cmat0, f.Rp, f.Cp);
     if (h->usesvd) {                                                                  // Cp (packed cmat0) is still needed
-        if (info != 0) { Rp.assign(P, 0.0); info = 0; }
-        info = host_initial_svd(d, h->cmat0, c.condmax, c.method == MCMCX_METHOD_SCAM, Rfull, qstd0);
+        if (info != 0) { f.Rp.assign(P, 0.0); info = 0; }
+        info = host_initial_svd(d, h->cmat0, c.condmax, c.method == MCMCX_METHOD_SCAM, f.Rfull, f.qstd);
     }
     if (info != 0) return fail(-32, "could not factor the initial covariance");      // MCMC_init.F90:110
-    h->S02eff = (c.S02 <= 0.0) ? h->sigma2 : c.S02;                                   // MCMC_init.F90:114-116
-    double shape = c.N0 / 2.0 + (double)h->nobs / 2.0;
-
+    if (h->pooled && (long long)c.nchains * (h->comm ? h->comm->nranks : 1) < 2)
+        return fail(-8, "pooled mode needs at least 2 chains over all ranks");
+    if (h->pooled && (phase_cut(h) || (h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM)))
+        return fail(-8, "pooled mode needs one of the single-launch device targets (gauss, banana, expdata, expcols; scam: not expcols)");
+    if (h->dodr) {                                      // iC = dpotri(R), R2 = R/drscale, MCMC_adapt.F90:216-225
+        f.iCp = f.Rp; f.R2p.resize(P);
+        if (h->usesvd) for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) f.iCp[h_pidx(i, j, d)] = f.Rfull[(size_t)j * d + i];
+        if (host_potri(d, f.iCp) != 0) return fail(-34, "ERROR: cannot invert cmat");
+        for (int e = 0; e < P; ++e) f.R2p[e] = f.Rp[e] / c.drscale;
+    }
+    if (h->external && h->pooled) return fail(-8, "mcmcx_set_target_external: not in pooled mode");
+    return 0;
+}
+static int init_engine_dev(mcmcx_engine *h, const InitialFactor &f)    // EngineDev's scalars, the target's and the problem's tables
+{
+    const mcmcx_config &c = h->cfg;
     EngineDev &E = h->E;
-    E.d = d; E.P = P; E.ntiles = T;
+    E = EngineDev{};                                    // every table nullptr until a step below allocates it
+    h->S02eff = (c.S02 <= 0.0) ? h->sigma2 : c.S02;                                   // MCMC_init.F90:114-116
+    E.d = h->d; E.P = h->P; E.ntiles = h->ntiles;
     E.method = kernel_method(h);
     E.usesvd = h->usesvd; E.doscam = (c.method == MCMCX_METHOD_SCAM) ? 1 : 0; E.condmax = c.condmax;
     E.scam_fast = c.scam_fast ? 1 : 0;
-    E.Rf = E.R2f = E.qstd = E.Gw = E.Vw = nullptr;
     E.greedy = c.greedy; E.adapthist = c.adapthist; E.initcmatn = (double)c.initcmatn;
     E.dodr = h->dodr; E.updatesigma = c.updatesigma; E.doadapt = c.doadapt; E.doburnin = c.doburnin; E.burnintime = c.burnintime;
-    E.gam_shape = shape; E.N0S02 = c.N0 * h->S02eff;
-    E.ny = ny; E.hs = d + ny; E.ssv = E.s2v = E.ss2v = nullptr; E.gshapev = nullptr;
+    E.gam_shape = c.N0 / 2.0 + (double)h->nobs / 2.0; E.N0S02 = c.N0 * h->S02eff;
+    E.ny = h->ny; E.hs = h->d + h->ny;
     E.alphatarget = c.alphatarget; E.drscale = c.drscale; E.scalelimit = c.scalelimit; E.scalefactor = c.scalefactor;
     E.k0 = c.seed; E.chain_id0 = c.chain_id0;
     E.dr_lds = h->plan.dr_lds ? 1 : 0;
     E.lds_scratch = h->plan.lds_form;
-    // target
     E.tgt.kind = phased(h) ? (int)TGT_HOST : h->tkind;   // the kernels know one phase-cut mode; who evaluates is the host's business
     E.tgt.b = h->tb; E.tgt.ndata = (int)h->tx.size(); E.tgt.ncols = h->tncols;
-    E.tgt.mu = E.tgt.x = E.tgt.y = E.tgt.lo = E.tgt.hi = E.tgt.pmu = E.tgt.psig = nullptr;
+    const int d = h->d;
     int rc;
-    E.tgt.lamT = nullptr;
     if (h->tkind == TGT_GAUSS) {
         if ((rc = dev_upload(h, &E.tgt.mu, h->tmu))) return rc;
         std::vector<double> lt((size_t)(d + 4) * d + 64, 0.0);     // transpose; zero pad rows + slack for the panel / MFMA tile reads
@@ -360,68 +377,49 @@ int mcmcx_init(mcmcx_handle h)
     if (h->has_pri) { if ((rc = dev_upload(h, &E.tgt.pmu, h->tpmu))) return rc; if ((rc = dev_upload(h, &E.tgt.psig, h->tpsig))) return rc;
         }
     if ((rc = dev_upload(h, &E.par0, h->par0))) return rc;
-    if ((rc = dev_upload(h, &E.cmat0p, Cp))) return rc;
-
-    // state
-    const size_t L = (size_t)T * 64;
+    return dev_upload(h, &E.cmat0p, f.Cp);
+}
+// the chains' state and scratch vectors, their SVD factors and the adaptation's work space, the delayed-rejection tables, the history
+// ring, AM's state
+static int init_chains(mcmcx_engine *h, const InitialFactor &f)
+{
+    const mcmcx_config &c = h->cfg;
+    EngineDev &E = h->E;
+    const int d = h->d, P = h->P, T = h->ntiles, ny = h->ny;
+    const size_t L = (size_t)T * 64, DD = (size_t)d * d;
+    int rc;
     if ((rc = dev_alloc(h, &E.theta, L * d))) return rc;
     if ((rc = h->plan.host_mapped ? host_alloc(h, &E.cand, L * d) : dev_alloc(h, &E.cand, L * d))) return rc;
     if ((rc = dev_alloc(h, &E.zs, L * 2 * d))) return rc;
     if ((rc = h->plan.cs_mapped ? host_alloc(h, &E.cs, L * 2 * d) : dev_alloc(h, &E.cs, L * 2 * d))) return rc;
-    E.xscr = nullptr;
-    // step_kernel_pooled_dr_big's quadratic-form vectors; npar > 320: adapt_post_kernel's work vector
-    if (((h->pooled && h->dodr) || d > 320) && (rc = dev_alloc(h, &E.xscr, L * 2 * d))) return rc;
+    if (h->plan.xscr && (rc = dev_alloc(h, &E.xscr, L * 2 * d))) return rc;
     if ((rc = dev_alloc(h, &E.scal, L * NSCAL))) return rc;
     if ((rc = dev_alloc(h, &E.ictr, L * NICTR))) return rc;
     if ((rc = dev_alloc(h, &E.rngn, L))) return rc;
-    E.R = nullptr;
     if (!h->pooled && (rc = dev_alloc(h, &E.R, L * P, false))) return rc;          // pooled: one shared factor instead
     if ((rc = dev_alloc(h, &E.basetheta, L * d))) return rc;
-    if (h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM) {     // pooled SCAM: one rotation for every chain
-        if (h->plan.scam_replicated) {
-            if ((rc = dev_alloc(h, &E.Rf, L * (size_t)d * d, false))) return rc;
-            if ((rc = dev_alloc(h, &E.qstd, L * d))) return rc;
-        } else if ((rc = dev_alloc(h, &h->d_sharedU, 2 * shared_u_stride(h) + d, false))) return rc;
-        h->pool_U = Rfull; h->pool_std = qstd0;
-        if ((rc = upload_shared_u(h))) return rc;
-    } else if (h->usesvd && h->pooled) {                // pooled AM with the SVD factor: one full matrix for every chain (below)
-        h->pool_Rf = Rfull;
-    } else if (h->usesvd) {
-        const size_t DD = (size_t)d * d;
+    if (h->usesvd && !h->pooled) {                      // (pooled: pooled_alloc)
         if ((rc = dev_alloc(h, &E.Rf, L * DD, false))) return rc;
         if (c.method != MCMCX_METHOD_RAM) {                 // work space of the adaptation's SVD; RAM never refactors
-            if ((rc = dev_alloc(h, &E.Gw, L * DD))) return rc;
-            if ((rc = dev_alloc(h, &E.Vw, L * DD))) return rc;
-            if (h->plan.svd_blocked) {                  // chain-major copies for svd_blocked_kernel
-                if ((rc = dev_alloc(h, &h->d_Gc, L * DD, false))) return rc;
-                if ((rc = dev_alloc(h, &h->d_Vc, L * DD, false))) return rc;
-                if ((rc = dev_alloc(h, &h->d_svc, L * d, false))) return rc;
-                if ((rc = dev_alloc(h, &h->d_need, L))) return rc;
-                if ((rc = dev_alloc(h, &h->d_state, L))) return rc;
-                if ((rc = dev_alloc(h, &h->d_anyrot, 1))) return rc;
-            }
+            if ((rc = dev_alloc(h, &E.Gw, L * DD)) || (rc = dev_alloc(h, &E.Vw, L * DD))) return rc;
+            if (h->plan.svd_blocked && ((rc = dev_alloc(h, &h->d_Gc, L * DD, false)) || (rc = dev_alloc(h, &h->d_Vc, L * DD, false))
+                || (rc = dev_alloc(h, &h->d_svc, L * d, false)) || (rc = dev_alloc(h, &h->d_need, L)) || (rc = dev_alloc(h, &h->d_state, L))
+                || (rc = dev_alloc(h, &h->d_anyrot, 1)))) return rc;    // chain-major copies for svd_blocked_kernel
         }
         if ((rc = dev_alloc(h, &E.qstd, L * d))) return rc;
         if (h->dodr && (rc = dev_alloc(h, &E.R2f, L * DD, false))) return rc;
-        if ((rc = dev_bcast(h, E.Rf, Rfull))) return rc;
-        if ((rc = dev_bcast(h, E.qstd, qstd0))) return rc;
+        if ((rc = dev_bcast(h, E.Rf, f.Rfull)) || (rc = dev_bcast(h, E.qstd, f.qstd))) return rc;
         if (h->dodr) {
-            std::vector<double> r2 = Rfull;
+            std::vector<double> r2 = f.Rfull;
             for (auto &v : r2) v = v / c.drscale;
             if ((rc = dev_bcast(h, E.R2f, r2))) return rc;
         }
     }
-    E.R2 = E.iC = nullptr;
-    if (h->dodr && !h->pooled) {                        // pooled: one R2 and one iC for every chain (below)
-        if ((rc = dev_alloc(h, &E.R2, L * P, false))) return rc;
-        if ((rc = dev_alloc(h, &E.iC, L * P, false))) return rc;
-    }
-    const bool am = (c.method != MCMCX_METHOD_RAM) && (c.doadapt != 0 || c.doburnin != 0) && !h->pooled;
-    E.cmat = E.mean = E.Rtmp = nullptr; E.rowlist = nullptr;
-    // history ring
-    const bool need_hist = am || c.record_chain;
-    h->wcap = 0; E.hist = E.s2hist = nullptr; E.wacc = nullptr; E.record_s2 = 0;
-    if (need_hist) {
+    // (pooled: one R2 and one iC for every chain, pooled_alloc)
+    if (h->dodr && !h->pooled && ((rc = dev_alloc(h, &E.R2, L * P, false)) || (rc = dev_alloc(h, &E.iC, L * P, false)))) return rc;
+    const bool am = h->plan.am;
+    h->wcap = 0;
+    if (am || c.record_chain) {                         // the history ring
         // AP windows (adapthist > 1) may reach back to an arbitrarily old row: keep everything.  Otherwise the longest
         // window is the first AM one, rows 2 .. T1 with T1 the first multiple of adaptint / badaptint that is
         // >= burnintime + adaptint + adapthist (MCMC_adapt.F90:42-46,105): up to adaptint - 1 iterations past that
@@ -435,44 +433,31 @@ int mcmcx_init(mcmcx_handle h)
         if (c.record_chain && c.updatesigma) { E.record_s2 = 1; if ((rc = dev_alloc(h, &E.s2hist, L * (size_t)h->wcap * ny))) return rc; }
     }
     E.wcap = h->wcap > 0 ? h->wcap : 1;
-    if (am) {
-        if ((rc = dev_alloc(h, &E.cmat, L * P))) return rc;
-        if ((rc = dev_alloc(h, &E.mean, L * d))) return rc;
-        if ((rc = dev_alloc(h, &E.Rtmp, L * P))) return rc;
-        if ((rc = dev_alloc(h, &E.rowlist, L * (size_t)(h->wcap + 1)))) return rc;
-    }
-    E.sharedR = nullptr;
-    if (h->pooled) {
-        if ((long long)c.nchains * (h->comm ? h->comm->nranks
-            : 1) < 2) return fail(-8, "pooled mode needs at least 2 chains over all ranks");
-        if (phase_cut(h) || (h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM))
-            return fail(-8, "pooled mode needs one of the single-launch device targets (gauss, banana, expdata, expcols; scam: not expcols)");
-        if ((rc = dev_alloc(h, &h->d_sharedR, (size_t)P, false))) return rc;
-        HIPCHK(hipMemcpy(h->d_sharedR, Rp.data(), (size_t)P * 8, hipMemcpyHostToDevice));
-        E.sharedR = h->d_sharedR;
-        h->pool_R = Rp; h->pool_C = Cp; h->pool_mean = h->par0; h->pool_W = (double)c.initcmatn;
-        if (c.method == MCMCX_METHOD_DRAM || c.method == MCMCX_METHOD_RAM || c.method == MCMCX_METHOD_ER) {
-            if ((rc = dev_alloc(h, &h->d_sharedRT, (size_t)((d + 3) & ~3) * d + PWS, false))) return rc;
-            if ((rc = h->usesvd ? upload_shared_rf(h) : upload_shared_rt(h))) return rc;
-            if (h->usesvd) E.sharedR = h->d_sharedRT;   // the lane-per-chain kernel reads the full matrix through the scalar cache
-        }
-    }
-    E.hev = E.hx = nullptr;
+    if (am && ((rc = dev_alloc(h, &E.cmat, L * P)) || (rc = dev_alloc(h, &E.mean, L * d)) || (rc = dev_alloc(h, &E.Rtmp, L * P))
+        || (rc = dev_alloc(h, &E.rowlist, L * (size_t)(h->wcap + 1))))) return rc;
+    return 0;
+}
+// the host-callback / response-column phase buffers, the accept records, the RAM step sizes, the pooled moments' workspace
+static int init_run_buffers(mcmcx_engine *h)
+{
+    const mcmcx_config &c = h->cfg;
+    EngineDev &E = h->E;
+    const int d = h->d, P = h->P, T = h->ntiles, ny = h->ny;
+    const size_t L = (size_t)T * 64;
+    int rc;
     if (phased(h)) {
         const size_t nhev = L * (NHE - 1 + ny);
         if ((rc = h->plan.host_mapped ? host_alloc(h, &E.hev, nhev) : dev_alloc(h, &E.hev, nhev))) return rc;
         if (ny > 1) {
-            if ((rc = dev_alloc(h, &E.ssv, L * ny))) return rc;
-            if ((rc = dev_alloc(h, &E.s2v, L * ny))) return rc;
-            if ((rc = dev_alloc(h, &E.ss2v, L * ny))) return rc;
-            if ((rc = dev_bcast(h, E.s2v, h->sigma2v))) return rc;
+            if ((rc = dev_alloc(h, &E.ssv, L * ny)) || (rc = dev_alloc(h, &E.s2v, L * ny)) || (rc = dev_alloc(h, &E.ss2v, L * ny))
+                || (rc = dev_bcast(h, E.s2v, h->sigma2v))) return rc;
             std::vector<double> gs(ny);
             for (int j = 0; j < ny; ++j) gs[j] = c.N0 / 2.0 + (double)h->nobsv[j] / 2.0;
             if ((rc = dev_upload(h, &E.gshapev, gs))) return rc;
         }
         if ((rc = h->plan.host_mapped ? host_alloc(h, &E.hx, L * NHX) : dev_alloc(h, &E.hx, L * NHX))) return rc;
     }
-    E.accmask = nullptr;
+    if (h->external && (rc = dev_alloc(h, &h->d_r1, L * (size_t)(3 * d + 3 * ny + NR1)))) return rc;   // MCMC_run1: run1_kernel's vectors
     if (c.record_accept && (rc = dev_alloc(h, &E.accmask, (size_t)c.nsimu * T))) return rc;
     // the lane-group kernels: accept bytes of a launch; the range flag of the power-of-two delayed-rejection form
     if ((h->plan.group_d4 || h->plan.ram_group_d4) && (E.hist || E.accmask)
@@ -486,65 +471,62 @@ int mcmcx_init(mcmcx_handle h)
         if ((rc = dev_upload(h, &p, rs))) return rc;
         h->d_ramscale = const_cast<double *>(p);
     }
-    // longest pooled vector: 2 + d + P
-    if ((rc = dev_alloc(h, &h->d_moments, (size_t)(T + 1) * (2 + d + P)))) return rc;
-    // longest vector + the stop flag
-    if ((rc = dev_alloc(h, &h->d_gather, (size_t)(h->comm ? h->comm->nranks : 1) * (3 + d + P)))) return rc;
-    if ((rc = dev_alloc(h, &h->d_pooled, (size_t)(3 + d + P)))) return rc;
-
-    // fill theta = par0, R = R(cmat0), chaincmat = cmat0, chainmean = par0, scalars
-    {
-        std::vector<double> sc(L * NSCAL, 0.0);
-        std::vector<uint32_t> ic(L * NICTR, 0u);
-        for (int t = 0; t < T; ++t)
-            for (int l = 0; l < 64; ++l) {
-                sc[((size_t)t * NSCAL + S_SIGMA2) * 64 + l] = h->sigma2;
-                sc[((size_t)t * NSCAL + S_WSUM) * 64 + l] = (double)c.initcmatn;
-                ic[((size_t)t * NICTR + I_CHAININD) * 64 + l] = 1;
-                ic[((size_t)t * NICTR + I_CURCOUNT) * 64 + l] = 1;
-                ic[((size_t)t * NICTR + I_BASECNT) * 64 + l] = 1;
-                ic[((size_t)t * NICTR + I_WINSTART) * 64 + l] = 2;
-            }
-        HIPCHK(hipMemcpyAsync(E.scal, sc.data(), sc.size() * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(E.ictr, ic.data(), ic.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if ((rc = dev_bcast(h, E.theta, h->par0))) return rc;
-        if (!h->pooled && (rc = dev_bcast(h, E.R, Rp))) return rc;
-        if (h->dodr) {                                   // iC = dpotri(R), R2 = R/drscale, MCMC_adapt.F90:216-225
-            std::vector<double> iCp = Rp, R2p(P);
-            if (h->usesvd) for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) iCp[h_pidx(i, j, d)] = Rfull[(size_t)j * d + i];
-            if (host_potri(d, iCp) != 0) return fail(-34, "ERROR: cannot invert cmat");
-            for (int e = 0; e < P; ++e) R2p[e] = Rp[e] / c.drscale;
-            if (h->pooled) {
-                h->pool_iC = iCp;
-                if (h->usesvd) { h->pool_R2 = Rfull; for (auto &v : h->pool_R2) v = v / c.drscale; } else h->pool_R2 = R2p;
-                if ((rc = dev_alloc(h, &h->d_sharedR2, h->usesvd ? (size_t)((d + 3) & ~3) * d + PWS : (size_t)P, false))) return rc;
-                if ((rc = dev_alloc(h, &h->d_sharediC, (size_t)P, false))) return rc;
-                if (h->plan.pooled_dr_mfma) {
-                    if ((rc = dev_alloc(h, &h->d_sharedR2T, (size_t)((d + 3) & ~3) * d + PWS, false))) return rc;
-                    if ((rc = dev_alloc(h, &h->d_sharediCd, (size_t)((d + 3) & ~3) * d + PWS, false))) return rc;
-                }
-                if ((rc = pooled_upload_dr(h, false))) return rc;
-            } else {
-            if ((rc = dev_bcast(h, E.R2, R2p))) return rc;
-            if ((rc = dev_bcast(h, E.iC, iCp))) return rc;
-            }
+    if ((rc = dev_alloc(h, &h->d_moments, (size_t)(T + 1) * (2 + d + P)))) return rc;                 // longest pooled vector: 2 + d + P
+    if ((rc = dev_alloc(h, &h->d_gather, (size_t)(h->comm ? h->comm->nranks : 1) * (3 + d + P)))) return rc;   // ... + the stop flag
+    return dev_alloc(h, &h->d_pooled, (size_t)(3 + d + P));
+}
+// fill theta = par0, R = R(cmat0), chaincmat = cmat0, chainmean = par0, scalars; the first evaluation
+static int init_fill(mcmcx_engine *h, const InitialFactor &f)
+{
+    const mcmcx_config &c = h->cfg;
+    EngineDev &E = h->E;
+    const int T = h->ntiles;
+    std::vector<double> sc((size_t)T * 64 * NSCAL, 0.0);
+    std::vector<uint32_t> ic((size_t)T * 64 * NICTR, 0u);
+    for (int t = 0; t < T; ++t)
+        for (int l = 0; l < 64; ++l) {
+            sc[((size_t)t * NSCAL + S_SIGMA2) * 64 + l] = h->sigma2;
+            sc[((size_t)t * NSCAL + S_WSUM) * 64 + l] = (double)c.initcmatn;
+            ic[((size_t)t * NICTR + I_CHAININD) * 64 + l] = 1;
+            ic[((size_t)t * NICTR + I_CURCOUNT) * 64 + l] = 1;
+            ic[((size_t)t * NICTR + I_BASECNT) * 64 + l] = 1;
+            ic[((size_t)t * NICTR + I_WINSTART) * 64 + l] = 2;
         }
-        if (am) {
-            if ((rc = dev_bcast(h, E.cmat, Cp))) return rc;
-            if ((rc = dev_bcast(h, E.mean, h->par0))) return rc;
-        }
-    }
-    if (h->external) {                                  // MCMC_run1: every evaluation is the caller's, the first one included
-        if (h->pooled) return fail(-8, "mcmcx_set_target_external: not in pooled mode");
-        if ((rc = dev_alloc(h, &h->d_r1, L * (size_t)(3 * d + 3 * ny + NR1)))) return rc;
-    } else if (phased(h)) {                             // first point: sspri1, ss1 from the callbacks (MCMC_run.F90:35-36)
-        int rc2 = host_eval(h, E.theta, d, false);
-        if (rc2) return rc2;
-    }
+    HIPCHK(hipMemcpyAsync(E.scal, sc.data(), sc.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(E.ictr, ic.data(), ic.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    int rc;
+    if ((rc = dev_bcast(h, E.theta, h->par0))) return rc;
+    if (!h->pooled && (rc = dev_bcast(h, E.R, f.Rp))) return rc;
+    if (h->dodr && !h->pooled && ((rc = dev_bcast(h, E.R2, f.R2p)) || (rc = dev_bcast(h, E.iC, f.iCp)))) return rc;
+    if (h->plan.am && ((rc = dev_bcast(h, E.cmat, f.Cp)) || (rc = dev_bcast(h, E.mean, h->par0)))) return rc;
+    // first point: sspri1, ss1 from the callbacks (MCMC_run.F90:35-36) -- with MCMC_run1 every evaluation is the caller's, this one too
+    if (!h->external && phased(h) && (rc = host_eval(h, E.theta, h->d, false))) return rc;
     launch_init(h);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int mcmcx_init(mcmcx_handle h)
+{
+    if (!h) return fail(-1, "null handle");
+    if (h->inited) return fail(1, "Warning(mcmcinit): allready inited");            // MCMC_init.F90:24-27
+    HIPCHK(hipSetDevice(h->cfg.device));
+    int rc = init_check(h);
+    if (rc) return rc;
+    plan_kernels(h);                                 // which kernels run: decided here, once; what follows allocates as the plan says
+    InitialFactor f;
+    if ((rc = initial_factor(h, f))) return rc;
+    if ((rc = init_engine_dev(h, f)) || (rc = init_chains(h, f))) return rc;
+    if (h->pooled) {                                 // the shared tables' masters as MCMC_init leaves a chain's, in the planned layouts
+        PooledState &s = h->pool;
+        s.R = f.Rp; s.C = f.Cp; s.mean = h->par0; s.W = (double)h->cfg.initcmatn;
+        if (h->cfg.method == MCMCX_METHOD_SCAM) { s.U = f.Rfull; s.std = f.qstd; } else s.Rf = f.Rfull;
+        if (h->dodr) pooled_dr_fresh(h);
+        if ((rc = pooled_alloc(h)) || (rc = pooled_upload(h))) return rc;
+    }
+    if ((rc = init_run_buffers(h)) || (rc = init_fill(h, f))) return rc;
     h->simuind = 1;
     h->inited = true;
     return 0;
@@ -774,7 +756,7 @@ int mcmcx_get_totals(mcmcx_handle h, int64_t *t7)
         t7[0] += at(I_STAYED); t7[1] += at(I_BNDSTAYED); t7[2] += at(I_DRACC); t7[3] += at(I_DRTRIES);
         t7[5] += at(I_DOWNS); t7[6] |= at(I_STATUS);
     }
-    t7[6] |= h->pool_status;                            // pooled RAM: a tick whose Gram matrix was not positive definite was skipped
+    t7[6] |= h->pool.status;                            // pooled RAM: a tick whose Gram matrix was not positive definite was skipped
     // proposals evaluated: one per iteration (d componentwise ones with method='scam') + the delayed-rejection tries
     t7[4] = (int64_t)h->cfg.nchains * (int64_t)(h->simuind - 1) * (h->cfg.method == MCMCX_METHOD_SCAM ? h->d : 1) + t7[3];
     return 0;
@@ -818,9 +800,7 @@ int mcmcx_get_R(mcmcx_handle h, int32_t chain, double *R)
 {
     int rc = check_chain(h, chain); if (rc) return rc;
     std::vector<double> p;
-    if (h->pooled && h->usesvd) { const auto &M = h->cfg.method == MCMCX_METHOD_SCAM ? h->pool_U : h->pool_Rf; memcpy(R, M.data(),
-        sizeof(double) * M.size()); return 0; }
-    if (h->pooled) { unpack_upper(h->d, h->pool_R, R, false); return 0; }
+    if (h->pooled) { pooled_out(h, pooled_R(h), !h->usesvd, R); return 0; }
     if (h->usesvd) {                                     // full column-major factor
         if ((rc = fetch_chain_vec(h, h->E.Rf, h->d * h->d, chain, p))) return rc;
         memcpy(R, p.data(), sizeof(double) * p.size());
@@ -834,8 +814,7 @@ int mcmcx_get_R(mcmcx_handle h, int32_t chain, double *R)
 int mcmcx_get_qcovstd(mcmcx_handle h, int32_t chain, double *std)
 {
     int rc = check_chain(h, chain); if (rc) return rc;
-    if (h->pooled && h->usesvd && h->cfg.method == MCMCX_METHOD_SCAM) { memcpy(std, h->pool_std.data(),
-        sizeof(double) * h->pool_std.size()); return 0; }
+    if (h->pooled && h->cfg.method == MCMCX_METHOD_SCAM) { pooled_out(h, h->pool.std, false, std); return 0; }
     if (!h->E.qstd) return fail(-45, "no SVD state (condmax = 0)");
     std::vector<double> p;
     if ((rc = fetch_chain_vec(h, h->E.qstd, h->d, chain, p))) return rc;
@@ -849,9 +828,8 @@ int mcmcx_get_dr(mcmcx_handle h, int32_t chain, double *R2, double *iC)
     if (!h->dodr) return fail(-43, "drscale = 0: no delayed-rejection state");
     std::vector<double> p;
     if (h->pooled) {                                    // one pair of tables for every chain
-        if (R2 && h->usesvd) memcpy(R2, h->pool_R2.data(), sizeof(double) * h->pool_R2.size());
-        else if (R2) unpack_upper(h->d, h->pool_R2, R2, false);
-        if (iC) unpack_upper(h->d, h->pool_iC, iC, false);
+        pooled_out(h, h->pool.R2, !h->usesvd, R2);
+        pooled_out(h, h->pool.iC, true, iC);
         return 0;
     }
     if (R2 && h->usesvd) { if ((rc = fetch_chain_vec(h, h->E.R2f, h->d * h->d, chain, p))) return rc; memcpy(R2, p.data(),
@@ -1008,13 +986,10 @@ int mcmcx_get_pooled(mcmcx_handle h, double *cmat, double *mean, double *wsum, d
 {
     if (!h || !h->inited) return fail(-40, "we have not inited");
     if (!h->pooled) return fail(-44, "not in pooled mode");
-    if (cmat) unpack_upper(h->d, h->pool_C, cmat, true);
-    if (mean) memcpy(mean, h->pool_mean.data(), sizeof(double) * (size_t)h->d);
-    if (wsum) *wsum = h->pool_W;
-    // scam: the rotation U; condmax > 0: the full SVD factor; column-major
-    if (R && h->usesvd) { const auto &M = h->cfg.method == MCMCX_METHOD_SCAM ? h->pool_U : h->pool_Rf; memcpy(R, M.data(),
-        sizeof(double) * M.size()); }
-    else if (R) unpack_upper(h->d, h->pool_R, R, false);
+    if (cmat) unpack_upper(h->d, h->pool.C, cmat, true);
+    if (mean) memcpy(mean, h->pool.mean.data(), sizeof(double) * (size_t)h->d);
+    if (wsum) *wsum = h->pool.W;
+    pooled_out(h, pooled_R(h), !h->usesvd, R);                  // scam: the rotation U; condmax > 0: the full SVD factor; column-major
     return 0;
 }
 

@@ -1,5 +1,5 @@
-// mcx_host_engine.hpp -- the engine object behind a mcmcx_handle: error reporting, the test switches, the host and device state of N
-// chains, allocation helpers.
+// mcx_host_engine.hpp -- the engine object behind a mcmcx_handle: error reporting, the test switches, the kernel plan, the host and device
+// state of N chains and pooled mode's shared tables (PooledState), allocation helpers.
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch,
 // mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
@@ -41,6 +41,8 @@ struct mcx_switches {
 // the plain lane step's LDS form (EngineDev::lds_scratch): nothing, the state and scratch vectors (step_kernel_ldsv), those and the packed
 // factor (step_kernel_ldsr); method = 'ram': the factor and its rotations (step_kernel_ram_ldsr)
 enum LdsForm { LDS_NONE = 0, LDS_STATE = 1, LDS_STATE_R = 2, LDS_RAM_R = 3 };
+// pooled mode's device layouts of the shared tables (PooledState), as KernelPlan::shared records which the planned kernel reads
+enum SharedLayout { SH_R = 1, SH_RT = 2, SH_DR = 4, SH_DRT = 8, SH_U = 16, SH_UREP = 32 };
 struct KernelEntry;
 // Which kernel forms the engine runs.  Decided ONCE, by plan_kernels at mcmcx_init (mcx_host_launch.hpp), from the configuration, the
 // problem's shape, the target kind, the switches and the CU count -- never from what was allocated; mcmcx_init allocates as it says and
@@ -67,9 +69,27 @@ struct KernelPlan {
     bool pooled_two_waves = false, pooled_forty_rows = false;
     bool ram_wide = false;              // method = 'ram' above RAM_SMALL_MAX through step_kernel_ram_wide
     bool scam_pooled12 = false, scam_fast_tile = false; int scam_waves = 1;
+    bool am = false;                    // the per-chain adaptation (not RAM, not pooled): covariance, mean and factor scratch per chain
+    bool xscr = false;                  // the chains' global scratch vectors (EngineDev::xscr): pooled DR, or npar > 320
+    unsigned shared = 0;                // pooled mode: the SharedLayout bits the chosen entry reads, all pooled_alloc allocates
     const KernelEntry *step = nullptr;  // what launch_step runs: a GROUP_TABLE entry when group_d4, a STEP_TABLE one otherwise
     const KernelEntry *scam = nullptr;  // what launch_scam runs
 };
+// Pooled mode (one proposal factor for all chains): the host masters the ticks compute (mcx_host_pooled.hpp) and the device layouts
+// pooled_upload writes from them.  Packed = the upper triangle (h_pidx); dense = M[s*d + o] = A(o, s) for the matrix A applied to z (R' of a
+// Cholesky factor, a full factor itself), npar rounded up to four rows, pad rows and PWS slack zero (dense_layout).
+struct PooledState {
+    int status = 0; double alpha = 0.0;                  // pooled RAM: skipped ticks, mean acceptance of the last tick
+    double W = 0.0; std::vector<double> mean, C, R;      // chainwsum, chainmean, chaincmat (packed), the Cholesky factor (packed)
+    std::vector<double> Rf;                              // condmax > 0: covtor_svd's full factor U sqrt(s) 2.4/sqrt(d), column-major
+    std::vector<double> U, std;                          // SCAM: the shared rotation (column-major) and qcovstd
+    std::vector<double> R2, iC;                          // delayed rejection: factor / drscale (stored like the factor), dpotri(R) packed
+    double *d_R = nullptr;                               // SH_R: R packed -- the lane kernels' E.sharedR, step_kernel_cols
+    double *d_RT = nullptr;                              // SH_RT: R or Rf dense -- pooled_mfma*_kernel; Rf: the lane kernels' E.sharedR
+    double *d_R2 = nullptr, *d_iC = nullptr;             // SH_DR: R2 (packed; Rf / drscale dense), iC packed -- *_pooled_dr*, _cols
+    double *d_R2T = nullptr, *d_iCd = nullptr;           // SH_DRT: R2 dense, iC dense and symmetric -- pooled_mfma_kernel<true>
+    double *d_U = nullptr;                               // SH_U: [U col-major | pad | U row-major | pad | std] -- scam_pooled[12]_kernel
+};                                                       // (SH_UREP: U and std copied to every chain's E.Rf / E.qstd -- npar > 240)
 struct mcmcx_engine {
     mcmcx_config cfg;
     KernelPlan plan;
@@ -108,25 +128,13 @@ struct mcmcx_engine {
         size_t size() const { return n; }
         void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = n = 0; }
     } h_cand, h_ev, h_hx;
-    // pooled mode
-    int pool_status = 0; double pool_alpha = 0.0;       // pooled RAM: skipped ticks, mean acceptance of the last tick
-    int pooled = 0; double pool_W = 0.0; std::vector<double> pool_mean, pool_C, pool_R;   // packed upper, row-major
-    std::vector<double> pool_U, pool_std;             // pooled SCAM: the shared rotation (column-major) and qcovstd
-    // pooled AM with condmax > 0: covtor_svd's full factor U sqrt(s) 2.4/sqrt(d), column-major
-    std::vector<double> pool_Rf;
-    // pooled mode with delayed rejection: R / drscale (packed, or full with condmax > 0) and dpotri(R) (packed)
-    std::vector<double> pool_R2, pool_iC;
-    double *d_sharedR2 = nullptr, *d_sharediC = nullptr;
-    double *d_sharedU = nullptr;                      // [U col-major | pad | U row-major | pad | std]
+    int pooled = 0; PooledState pool;                 // pooled mode
     // host callbacks: the next iteration's proposal already ran in the previous iteration's last launch
     bool p0_done = false;
     // a host-callback iteration failed half way: the chains' stream positions are undefined, later runs are refused
     bool failed = false;
     std::vector<void *> hallocs;
-    // pooled AM on the matrix cores: dense R, M[s*d + o] = R(s,o), zero below the diagonal and in the pad rows
-    double *d_sharedRT = nullptr;
-    double *d_sharedR2T = nullptr, *d_sharediCd = nullptr;   // ... with delayed rejection: R2 in the same form, iC dense and symmetric
-    double *d_sharedR = nullptr; mcmcx_exchange_t xfn = nullptr; void *xuser = nullptr; double *xbuf = nullptr;
+    mcmcx_exchange_t xfn = nullptr; void *xuser = nullptr; double *xbuf = nullptr;
     struct mcmcx_comm *comm = nullptr;                // the node's communicator (mcx_comm.hpp); nullptr = this GPU alone
     // [nranks][len + 1] per-rank moment vectors (+ the rank's stop flag), [len + 1] their tree sum
     double *d_gather = nullptr, *d_pooled = nullptr;

@@ -1,6 +1,6 @@
-// mcx_host_launch.hpp -- which kernels run: the three selection tables (step / group / scam) and their launchers, the shared tables'
-// uploads, and plan_kernels -- the one place that reads the test switches and holds the "where it wins" rules, run once at mcmcx_init;
-// its KernelPlan (mcx_host_engine.hpp) is all the launchers and mcmcx_init consult.
+// mcx_host_launch.hpp -- which kernels run: the three selection tables (step / group / scam) and their launchers -- each pooled entry
+// naming the shared layouts it reads -- and plan_kernels, the one place that reads the test switches and holds the "where it wins" rules,
+// run once at mcmcx_init; its KernelPlan (mcx_host_engine.hpp) is all the launchers, mcmcx_init and pooled_alloc consult.
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch,
 // mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
@@ -66,6 +66,7 @@ struct KernelEntry {
     const char *name;
     bool (*when)(const mcmcx_engine *);
     void (*launch)(mcmcx_engine *, int it0, int it1);
+    unsigned shared = 0;                                  // pooled mode: the SharedLayout bits its kernel reads (SH_R: E.sharedR's factor)
 };
 static const KernelEntry *pick_entry(const mcmcx_engine *h, const KernelEntry *tab, size_t n)
 {
@@ -300,35 +301,35 @@ static const KernelEntry STEP_TABLE[] = {
          (const double *)h->d_ramscale, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
     {"step", "step_kernel_cols", [](const mcmcx_engine *h) { return h->plan.fused_cols; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<0>, G1, lds_step(h), STEP_ARGS,
-         (const double *)h->d_ramscale, (const double *)(h->pooled ? h->E.sharedR : nullptr), (const double *)h->d_sharedR2,
-         (const double *)h->d_sharediC); }},
+         (const double *)h->d_ramscale, (const double *)(h->pooled ? h->E.sharedR : nullptr), (const double *)h->pool.d_R2,
+         (const double *)h->pool.d_iC); }, SH_R | SH_DR},
     // ---- pooled mode (one shared factor)
     {"step", "pooled_mfma_kernel<true>", [](const mcmcx_engine *h) { return h->plan.pooled_dr_mfma; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<true>, G1, pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT,
-         h->d_sharedRT, h->d_sharedR2T, h->d_sharediCd); }},
+         h->pool.d_RT, h->pool.d_R2T, h->pool.d_iCd); }, SH_RT | SH_DRT},
     MCX_VARIANT_STEP_ENTRIES
     {"step", "pooled_mfma_ks_kernel", [](const mcmcx_engine *h) { return h->plan.pooled_forty_rows; },
      [](mcmcx_engine *h, int it0, int it1) {
          // (npar 49..52: the fourth output block has four rows and goes through the 4 x 4 x 4 instruction)
          const size_t lds = (size_t)PKS * 64 * sizeof(double);
-         if (((h->d + 3) & ~3) == 52) hipLaunchKernelGGL(pooled_mfma_ks_kernel<true>, G1, lds, STEP_ARGS, STEP_TGT, h->d_sharedRT);
-         else hipLaunchKernelGGL(pooled_mfma_ks_kernel<false>, G1, lds, STEP_ARGS, STEP_TGT, h->d_sharedRT); }},
+         if (((h->d + 3) & ~3) == 52) hipLaunchKernelGGL(pooled_mfma_ks_kernel<true>, G1, lds, STEP_ARGS, STEP_TGT, h->pool.d_RT);
+         else hipLaunchKernelGGL(pooled_mfma_ks_kernel<false>, G1, lds, STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT},
     {"step", "pooled_mfma_kernel<false, true>", [](const mcmcx_engine *h) {
         return h->plan.pooled_mfma && h->plan.pooled_two_waves; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((pooled_mfma_kernel<false, true>), G1, pooled_mfma_lds(h->d), STEP_ARGS,
-         STEP_TGT, h->d_sharedRT, (const double *)nullptr, (const double *)nullptr); }},
+         STEP_TGT, h->pool.d_RT, (const double *)nullptr, (const double *)nullptr); }, SH_RT},
     {"step", "pooled_mfma_kernel<false>", [](const mcmcx_engine *h) { return h->plan.pooled_mfma; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<false>, G1, pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT,
-         h->d_sharedRT, (const double *)nullptr, (const double *)nullptr); }},
+         h->pool.d_RT, (const double *)nullptr, (const double *)nullptr); }, SH_RT},
     {"step", "step_kernel_pooled_dr_big", [](const mcmcx_engine *h) { return h->pooled && h->dodr && !h->plan.dr_vectors_in_lds; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_pooled_dr_big, G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR, h->d_sharedR2, h->d_sharediC); }},
+         h->E.sharedR, h->pool.d_R2, h->pool.d_iC); }, SH_R | SH_DR},
     {"step", "step_kernel_pooled_dr", [](const mcmcx_engine *h) { return h->pooled && h->dodr; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_pooled_dr, G1, lds_step(h), STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR, h->d_sharedR2, h->d_sharediC); }},
+         h->E.sharedR, h->pool.d_R2, h->pool.d_iC); }, SH_R | SH_DR},
     {"step", "step_kernel<false, false, true>", [](const mcmcx_engine *h) { return h->pooled != 0; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<false, false, true>), G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR); }},
+         h->E.sharedR); }, SH_R},
     // ---- method = 'ram', per-chain factors
     {"step", "group_ram_kernel", [](const mcmcx_engine *h) { return h->plan.ram_group_d4 != 0; }, launch_group_ram},
     {"step", "step_kernel_ram_fullr", [](const mcmcx_engine *h) { return kernel_method(h) == M_RAM && h->usesvd; },
@@ -382,44 +383,11 @@ static int dev_bcast(mcmcx_engine *h, double *dst, const std::vector<double> &v)
     if (e != hipSuccess) return fail(-100, hipGetErrorString(e));
     return 0;
 }
-static int upload_shared_rt(mcmcx_engine *h)
-{
-    const int d = h->d, d4 = (d + 3) & ~3;
-    std::vector<double> m((size_t)d4 * d + PWS, 0.0);
-    for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) m[(size_t)i * d + j] = h->pool_R[h_pidx(i, j, d)];
-    HIPCHK(hipMemcpyAsync(h->d_sharedRT, m.data(), m.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-static int upload_shared_rf(mcmcx_engine *h)            // dense M[s*d + o] = Rf(o, s): the column-major factor as it stands, pad rows zero
-{
-    const int d = h->d, d4 = (d + 3) & ~3;
-    std::vector<double> m((size_t)d4 * d + PWS, 0.0);
-    memcpy(m.data(), h->pool_Rf.data(), (size_t)d * d * 8);
-    HIPCHK(hipMemcpyAsync(h->d_sharedRT, m.data(), m.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-// d4 rows (pad rows zero) + slack
-static size_t shared_u_stride(const mcmcx_engine *h) { return (size_t)((h->d + 3) & ~3) * h->d + PWS; }
+// the dense layout's length (PooledState): d4 rows (pad rows zero) + slack; the stride of pooled SCAM's U block
+static size_t dense_len(const mcmcx_engine *h) { return (size_t)((h->d + 3) & ~3) * h->d + PWS; }
 // X [16 nt][64], Q [4 nt][64], zb, fl, mu [16 nt]
 static size_t scam_pooled_lds(int d) {
     return ((size_t)((d + 15) / 16) * (16 + 4) * 64 + 128 + (size_t)((d + 15) / 16) * 16) * sizeof(double); }
-static int upload_shared_u(mcmcx_engine *h)
-{
-    if (h->plan.scam_replicated) {                           // every chain's own copy of the one rotation and its scales
-        int rc = dev_bcast(h, h->E.Rf, h->pool_U); if (rc) return rc;
-        return dev_bcast(h, h->E.qstd, h->pool_std);
-    }
-    const int d = h->d; const size_t st = shared_u_stride(h);
-    std::vector<double> b(2 * st + d, 0.0);
-    for (int j = 0; j < d; ++j) for (int i = 0; i < d; ++i) { b[(size_t)j * d + i] = h->pool_U[(size_t)j * d + i];
-        b[st + (size_t)i * d + j] = h->pool_U[(size_t)j * d + i]; }
-    for (int i = 0; i < d; ++i) b[2 * st + i] = h->pool_std[i];
-    HIPCHK(hipMemcpyAsync(h->d_sharedU, b.data(), b.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-}
 // 13..15 output blocks (npar 193..240): twelve waves of 170 registers (scam_pooled12_kernel) instead of sixteen of 128
 static bool scam_use_12(const mcmcx_engine *h, const mcx_switches &sw)
 {
@@ -449,36 +417,37 @@ static int scam_tile_waves(const mcmcx_engine *h, const mcx_switches &sw)
     return nw;
 }
 #define SCAM_POOLED_ARGS scam_pooled_lds(h->d), h->stream, h->E, it0, it1, h->E.tgt.mu, h->E.tgt.lamT
+// (SH_UREP: the per-chain kernels read every chain's own rotation, E.Rf / E.qstd -- in pooled mode above npar 240, copies of the one)
 static const KernelEntry SCAM_TABLE[] = {
     {"scam", "step_kernel_cols<scam>", [](const mcmcx_engine *h) { return h->plan.fused_cols && !h->pooled; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<2>, G1, 0, STEP_ARGS, (const double *)h->d_ramscale,
          (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
     // pooled: 16-row output blocks, min(12, 4*(nt/4)) block waves + 4 chain-group waves; twelve waves of 170 registers for 13..15 blocks
     {"scam", "scam_pooled12_kernel", [](const mcmcx_engine *h) { return h->pooled && !h->plan.scam_replicated && h->plan.scam_pooled12; },
-     [](mcmcx_engine *h, int it0, int it1) { const size_t st = shared_u_stride(h);
-        hipLaunchKernelGGL(scam_pooled12_kernel, dim3(h->ntiles), dim3(768), SCAM_POOLED_ARGS, h->d_sharedU, h->d_sharedU + st,
-            h->d_sharedU + 2 * st); }},
+     [](mcmcx_engine *h, int it0, int it1) { const size_t st = dense_len(h);
+        hipLaunchKernelGGL(scam_pooled12_kernel, dim3(h->ntiles), dim3(768), SCAM_POOLED_ARGS, h->pool.d_U, h->pool.d_U + st,
+            h->pool.d_U + 2 * st); }, SH_U},
     {"scam", "scam_pooled_kernel", [](const mcmcx_engine *h) { return h->pooled && !h->plan.scam_replicated; },
-     [](mcmcx_engine *h, int it0, int it1) { const size_t st = shared_u_stride(h); const int nw = 4 + std::min(12, ((h->d + 15) / 16) & ~3);
-        hipLaunchKernelGGL(scam_pooled_kernel, dim3(h->ntiles), dim3(64 * nw), SCAM_POOLED_ARGS, h->d_sharedU, h->d_sharedU + st,
-            h->d_sharedU + 2 * st); }},
+     [](mcmcx_engine *h, int it0, int it1) { const size_t st = dense_len(h); const int nw = 4 + std::min(12, ((h->d + 15) / 16) & ~3);
+        hipLaunchKernelGGL(scam_pooled_kernel, dim3(h->ntiles), dim3(64 * nw), SCAM_POOLED_ARGS, h->pool.d_U, h->pool.d_U + st,
+            h->pool.d_U + 2 * st); }, SH_U},
     // (the sixteen-wave layout whatever npar: every lane fetches the column of its own chain's factor per sub-step, and four
     //  waves per SIMD cover that better than three -- 4.62e8 against 4.45e8 proposals/s at npar 200)
     {"scam", "scam_pooled_kernel<per-chain>", [](const mcmcx_engine *h) { return h->plan.scam_fast_tile; },
      [](mcmcx_engine *h, int it0, int it1) { const int nw = 4 + std::min(12, ((h->d + 15) / 16) & ~3);
         hipLaunchKernelGGL(scam_pooled_kernel, dim3(h->ntiles), dim3(64 * nw), SCAM_POOLED_ARGS, (const double *)nullptr,
-            (const double *)nullptr, (const double *)nullptr); }},
+            (const double *)nullptr, (const double *)nullptr); }, SH_UREP},
     {"scam", "scam_mw_kernel<8>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 8; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<8>, dim3(h->ntiles), dim3(512), scam_mw_lds(h), STEP_ARGS,
-         STEP_TGT); }},
+         STEP_TGT); }, SH_UREP},
     {"scam", "scam_mw_kernel<4>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 4; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<4>, dim3(h->ntiles), dim3(256), scam_mw_lds(h), STEP_ARGS,
-         STEP_TGT); }},
+         STEP_TGT); }, SH_UREP},
     {"scam", "scam_mw_kernel<2>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 2; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<2>, dim3(h->ntiles), dim3(128), scam_mw_lds(h), STEP_ARGS,
-         STEP_TGT); }},
+         STEP_TGT); }, SH_UREP},
     {"scam", "scam_kernel", [](const mcmcx_engine *) { return true; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_kernel, G1, 0, STEP_ARGS, STEP_TGT); }},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_kernel, G1, 0, STEP_ARGS, STEP_TGT); }, SH_UREP},
 };
 static void launch_scam(mcmcx_engine *h, int it0, int it1) { launch_entry(h, h->plan.scam, "scam", it0, it1); }
 // the adaptation's SVD one workgroup per chain (mcx_svd.hpp) where its rings and row groups are instantiated
@@ -500,7 +469,9 @@ static void plan_kernels(mcmcx_engine *h)
     p = KernelPlan();
     const mcmcx_config &c = h->cfg;
     const int d = h->d, P = h->P, T = h->ntiles;
-    const bool am = (c.method != MCMCX_METHOD_RAM) && (c.doadapt != 0 || c.doburnin != 0) && !h->pooled;
+    const bool am = p.am = (c.method != MCMCX_METHOD_RAM) && (c.doadapt != 0 || c.doburnin != 0) && !h->pooled;
+    // step_kernel_pooled_dr_big's and pooled_mfma_kernel<true>'s quadratic-form vectors; npar > 320: adapt_post_kernel's work vector
+    p.xscr = (h->pooled && h->dodr) || d > 320;
     p.dr_lds = h->dodr && dr_fits_lds(h);
     p.dr_vectors_in_lds = dr_vectors_in_lds(h, sw, h->pooled ? 4 : 8);
     {   // plain AM / Metropolis / ER step kernel: state and scratch vectors in LDS (4 d x 512 bytes per wave) when that costs no
@@ -578,4 +549,8 @@ static void plan_kernels(mcmcx_engine *h)
     if (c.method == MCMCX_METHOD_SCAM) p.scam = pick_entry(h, SCAM_TABLE, sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]));
     else if (p.group_d4) p.step = pick_entry(h, GROUP_TABLE, sizeof(GROUP_TABLE) / sizeof(GROUP_TABLE[0]));
     else p.step = pick_entry(h, STEP_TABLE, sizeof(STEP_TABLE) / sizeof(STEP_TABLE[0]));
+    // pooled mode: the shared layouts that entry reads (no R2 / iC without DR; the lane kernels read the SVD factor in the dense layout)
+    const KernelEntry *e = c.method == MCMCX_METHOD_SCAM ? p.scam : p.step;
+    p.shared = (h->pooled && e) ? e->shared & (h->dodr ? ~0u : ~(unsigned)(SH_DR | SH_DRT)) : 0;
+    if (h->usesvd && (p.shared & SH_R)) p.shared ^= SH_R | SH_RT;
 }

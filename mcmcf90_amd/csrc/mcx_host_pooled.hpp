@@ -1,4 +1,5 @@
-// mcx_host_pooled.hpp -- fetch helpers, signals, the communicator (mcx_comm.hpp), pooled mode's ticks: moments -> all-gather -> tree -> factor (pooled_tick, pooled_ram_tick).
+// mcx_host_pooled.hpp -- fetch helpers, signals, the communicator (mcx_comm.hpp), pooled mode's shared tables (pooled_alloc, pooled_upload)
+// and ticks: moments -> all-gather -> tree -> factor (pooled_tick, pooled_ram_tick).
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch, mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
 // ------------------------------------------------------------------ getters
@@ -112,52 +113,98 @@ static int pooled_reduce(mcmcx_engine *h, int kind, int it, std::vector<double> 
     return 0;
 }
 
-// Delayed rejection in pooled mode (MCMC_adapt.F90:216-225 once for all chains): R2 = R / drscale, iC = dpotri('U', R) on
-// the upper triangle of the factor as it stands.  fresh: a new factor (recompute both); otherwise the burn-in scaling
-// has already been applied to the tables themselves, as MCMC_adapt.F90:66-78 does.
-static int pooled_upload_dr(mcmcx_engine *h, bool fresh)
+// ------------------------------------------------------------------ the shared tables (PooledState)
+enum { PK_UPPER, PK_SYM, COLMAJOR };                    // the form of a master: packed upper triangle, packed symmetric, column-major d x d
+// the dense layout (PooledState) of a master: M[s*d + o] = A(o, s) -- R' of a packed factor, iC mirrored, a column-major matrix as it is
+static std::vector<double> dense_layout(int d, const std::vector<double> &m, int form)
 {
-    if (!h->dodr) return 0;
-    const int d = h->d, P = h->P;
-    if (fresh) {
-        std::vector<double> iC(P);
-        if (h->usesvd) {
-            h->pool_R2 = h->pool_Rf;
-            for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) iC[h_pidx(i, j, d)] = h->pool_Rf[(size_t)j * d + i];
-        } else { h->pool_R2 = h->pool_R; iC = h->pool_R; }
-        for (auto &v : h->pool_R2) v = v / h->cfg.drscale;
-        // the reference stops ("cannot invert cmat"); the old iC stays
-        if (host_potri(d, iC) != 0) h->pool_status |= ST_POTRI_FAIL;
-        else h->pool_iC = iC;
-    }
-    std::vector<double> r2 = h->pool_R2;
-    if (h->usesvd) r2.resize((size_t)((d + 3) & ~3) * d + PWS, 0.0);
-    HIPCHK(hipMemcpyAsync(h->d_sharedR2, r2.data(), r2.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_sharediC, h->pool_iC.data(), (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    // pooled_mfma_kernel<true>: R2 like d_sharedRT (M[s*d + o] = R2(s,o)), iC dense symmetric
-    if (h->plan.pooled_dr_mfma) {
-        const int d4 = (d + 3) & ~3;
-        std::vector<double> m((size_t)d4 * d + PWS, 0.0), q((size_t)d4 * d + PWS, 0.0);
-        // the full factor as it stands: M[s*d + o] = R2f(o, s)
-        if (h->usesvd) memcpy(m.data(), h->pool_R2.data(), (size_t)d * d * 8);
-        else for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) m[(size_t)i * d + j] = h->pool_R2[h_pidx(i, j, d)];
-        for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) { const double v = h->pool_iC[h_pidx(i, j, d)]; q[(size_t)i * d + j] = v;
-            q[(size_t)j * d + i] = v; }
-        HIPCHK(hipMemcpyAsync(h->d_sharedR2T, m.data(), m.size() * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_sharediCd, q.data(), q.size() * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
+    std::vector<double> M((size_t)((d + 3) & ~3) * d + PWS, 0.0);
+    if (form == COLMAJOR) memcpy(M.data(), m.data(), (size_t)d * d * 8);
+    else for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) { M[(size_t)i * d + j] = m[h_pidx(i, j, d)];
+        if (form == PK_SYM) M[(size_t)j * d + i] = m[h_pidx(i, j, d)]; }
+    return M;
+}
+// the layouts the plan records (KernelPlan::shared) and nothing else; E.sharedR is the lane kernels' factor: the packed R, or the dense
+// full factor with condmax > 0 (nullptr where the planned kernel reads neither)
+static int pooled_alloc(mcmcx_engine *h)
+{
+    PooledState &s = h->pool;
+    const unsigned L = h->plan.shared;
+    const size_t dn = dense_len(h), P = (size_t)h->P, d = (size_t)h->d, n = (size_t)h->nlanes;
+    int rc = 0;
+    if ((L & SH_R) && (rc = dev_alloc(h, &s.d_R, P, false))) return rc;
+    if ((L & SH_RT) && (rc = dev_alloc(h, &s.d_RT, dn, false))) return rc;
+    if ((L & SH_DR) && ((rc = dev_alloc(h, &s.d_R2, h->usesvd ? dn : P, false)) || (rc = dev_alloc(h, &s.d_iC, P, false)))) return rc;
+    if ((L & SH_DRT) && ((rc = dev_alloc(h, &s.d_R2T, dn, false)) || (rc = dev_alloc(h, &s.d_iCd, dn, false)))) return rc;
+    if ((L & SH_U) && (rc = dev_alloc(h, &s.d_U, 2 * dn + d, false))) return rc;
+    if ((L & SH_UREP) && ((rc = dev_alloc(h, &h->E.Rf, n * d * d, false)) || (rc = dev_alloc(h, &h->E.qstd, n * d)))) return rc;
+    h->E.sharedR = h->usesvd ? s.d_RT : s.d_R;
     return 0;
 }
-
-static int pooled_upload_R(mcmcx_engine *h)
+// every layout the plan records, written from the masters as they stand, with ONE synchronisation (the staging lives until then);
+// the per-chain copies above npar 240 go out through dev_bcast
+static int pooled_upload(mcmcx_engine *h)
 {
-    if (h->usesvd) return upload_shared_rf(h);
-    HIPCHK(hipMemcpyAsync(h->d_sharedR, h->pool_R.data(), (size_t)h->P * 8, hipMemcpyHostToDevice, h->stream));
+    const PooledState &s = h->pool;
+    const unsigned L = h->plan.shared;
+    const int d = h->d, form = h->usesvd ? COLMAJOR : PK_UPPER;
+    if (L & SH_UREP) { int rc = dev_bcast(h, h->E.Rf, s.U); return rc ? rc : dev_bcast(h, h->E.qstd, s.std); }
+    std::vector<std::vector<double>> st;
+    st.reserve(6);
+    auto put = [&](double *dst, std::vector<double> v) {
+        st.push_back(std::move(v));
+        return hipMemcpyAsync(dst, st.back().data(), st.back().size() * 8, hipMemcpyHostToDevice, h->stream);
+    };
+    if (L & SH_R) HIPCHK(put(s.d_R, s.R));
+    if (L & SH_RT) HIPCHK(put(s.d_RT, dense_layout(d, h->usesvd ? s.Rf : s.R, form)));
+    if (L & SH_DR) { HIPCHK(put(s.d_R2, h->usesvd ? dense_layout(d, s.R2, COLMAJOR) : s.R2)); HIPCHK(put(s.d_iC, s.iC)); }
+    if (L & SH_DRT) { HIPCHK(put(s.d_R2T, dense_layout(d, s.R2, form))); HIPCHK(put(s.d_iCd, dense_layout(d, s.iC, PK_SYM))); }
+    if (L & SH_U) {
+        const size_t sd = dense_len(h);
+        std::vector<double> b = dense_layout(d, s.U, COLMAJOR);
+        b.resize(2 * sd + d, 0.0);
+        for (int j = 0; j < d; ++j) for (int i = 0; i < d; ++i) b[sd + (size_t)i * d + j] = s.U[(size_t)j * d + i];
+        for (int i = 0; i < d; ++i) b[2 * sd + i] = s.std[i];
+        HIPCHK(put(s.d_U, std::move(b)));
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->d_sharedRT) return upload_shared_rt(h);
     return 0;
+}
+// Delayed rejection in pooled mode (MCMC_adapt.F90:216-225 once for all chains): R2 = R / drscale, iC = dpotri('U', R) on the upper
+// triangle of the factor as it stands
+static void pooled_dr_fresh(mcmcx_engine *h)
+{
+    PooledState &s = h->pool;
+    const int d = h->d;
+    std::vector<double> iC(h->P);
+    if (h->usesvd) {
+        s.R2 = s.Rf;
+        for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) iC[h_pidx(i, j, d)] = s.Rf[(size_t)j * d + i];
+    } else { s.R2 = s.R; iC = s.R; }
+    for (auto &v : s.R2) v = v / h->cfg.drscale;
+    // the reference stops ("cannot invert cmat"); the old iC stays
+    if (host_potri(d, iC) != 0) s.status |= ST_POTRI_FAIL;
+    else s.iC = iC;
+}
+// the burn-in's scaling of the shared factor, down (/ sf) or up (* sf); R2 and iC are scaled themselves (MCMC_adapt.F90:66-78)
+static void pooled_scale(mcmcx_engine *h, bool down)
+{
+    PooledState &s = h->pool;
+    const double sf = h->cfg.scalefactor;
+    for (auto &r : (h->usesvd ? s.Rf : s.R)) r = down ? r / sf : r * sf;
+    if (!h->dodr) return;
+    for (auto &r : s.R2) r = down ? r / sf : r * sf;
+    for (auto &r : s.iC) r = down ? r * sf * sf : r / sf / sf;
+}
+// the shared factor's master (SCAM: the rotation U; condmax > 0: the full factor Rf; otherwise the packed R), and a master out to the
+// caller: unpacked to column-major d x d when packed, as it is otherwise
+static const std::vector<double> &pooled_R(const mcmcx_engine *h)
+{ return h->cfg.method == MCMCX_METHOD_SCAM ? h->pool.U : h->usesvd ? h->pool.Rf : h->pool.R; }
+static void pooled_out(const mcmcx_engine *h, const std::vector<double> &m, bool packed, double *out)
+{
+    if (!out) return;
+    if (packed) unpack_upper(h->d, m, out, false);
+    else memcpy(out, m.data(), sizeof(double) * m.size());
 }
 
 // chaincmat -> the shared proposal factor (MCMC_calculate_R): dpotf2 + 2.4/sqrt(d), or the pinned SVD for scam; on
@@ -166,26 +213,22 @@ static int pooled_factor(mcmcx_engine *h)
 {
     const mcmcx_config &c = h->cfg;
     const int d = h->d;
-    std::vector<double> cm((size_t)d * d, 0.0), Rp, Cp;
-    for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) cm[(size_t)i + (size_t)j * d] = h->pool_C[h_pidx(i, j, d)];
+    PooledState &s = h->pool;
+    std::vector<double> cm((size_t)d * d, 0.0), F, Cp, sd, fc;
+    for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) cm[(size_t)i + (size_t)j * d] = s.C[h_pidx(i, j, d)];
     if (c.method == MCMCX_METHOD_SCAM) {                // scam_svd of the pooled covariance, MCMC_adapt.F90:189-200
-        std::vector<double> U, sd;
-        if (host_initial_svd(d, cm, c.condmax, true, U, sd) == 0) { h->pool_U = U; h->pool_std = sd; return upload_shared_u(h); }
-        return 0;
+        if (host_initial_svd(d, cm, c.condmax, true, F, sd) != 0) return 0;
+        s.U = F; s.std = sd;
+    } else if (h->usesvd) {                             // covtor_svd of the pooled covariance, MCMC_adapt.F90:203-209
+        if (host_initial_svd(d, cm, c.condmax, false, F, sd, &fc) != 0) return 0;
+        s.Rf = F;
+        if (!fc.empty()) for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) s.C[h_pidx(i, j, d)] = fc[(size_t)i + (size_t)j * d];
+    } else {
+        if (host_initial_R(d, cm, F, Cp) != 0) return 0;
+        s.R = F;
     }
-    if (h->usesvd) {                                    // covtor_svd of the pooled covariance, MCMC_adapt.F90:203-209
-        std::vector<double> Rf, sd, fc;
-        if (host_initial_svd(d, cm, c.condmax, false, Rf, sd, &fc) == 0) {
-            h->pool_Rf = Rf;
-            if (!fc.empty()) for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) h->pool_C[h_pidx(i, j,
-                d)] = fc[(size_t)i + (size_t)j * d];
-            int rc = pooled_upload_R(h);
-            return rc ? rc : pooled_upload_dr(h, true);
-        }
-        return 0;
-    }
-    if (host_initial_R(d, cm, Rp, Cp) == 0) { h->pool_R = Rp; int rc = pooled_upload_R(h); return rc ? rc : pooled_upload_dr(h, true); }
-    return 0;
+    if (h->dodr) pooled_dr_fresh(h);
+    return pooled_upload(h);
 }
 
 // merge the batch of n unit-weight rows (moments v about par0) into (chaincmat, chainmean, chainwsum): covmat's
@@ -202,30 +245,30 @@ static void pooled_merge(mcmcx_engine *h, const std::vector<double> &v, bool rep
             double s2 = v[1 + d + j * (j + 1) / 2 + i];
             Cb[h_pidx(i, j, d)] = (s2 - n * m1[i] * m1[j]) / (n - 1.0);
         }
-    if (replace || !(h->pool_W > 0.0)) {
-        h->pool_C = Cb; h->pool_mean = mb; h->pool_W = n;
+    if (replace || !(h->pool.W > 0.0)) {
+        h->pool.C = Cb; h->pool.mean = mb; h->pool.W = n;
     } else {
-        const double W = h->pool_W, Wn = W + n;
+        const double W = h->pool.W, Wn = W + n;
         std::vector<double> dl(d);
-        for (int j = 0; j < d; ++j) dl[j] = mb[j] - h->pool_mean[j];
+        for (int j = 0; j < d; ++j) dl[j] = mb[j] - h->pool.mean[j];
         const double f = W * n / Wn;
         for (int j = 0; j < d; ++j)
             for (int i = 0; i <= j; ++i) {
                 const int e = h_pidx(i, j, d);
-                h->pool_C[e] = ((W - 1.0) * h->pool_C[e] + (n - 1.0) * Cb[e] + f * dl[i] * dl[j]) / (Wn - 1.0);
+                h->pool.C[e] = ((W - 1.0) * h->pool.C[e] + (n - 1.0) * Cb[e] + f * dl[i] * dl[j]) / (Wn - 1.0);
             }
         const double g = n / Wn;
-        for (int j = 0; j < d; ++j) h->pool_mean[j] = h->pool_mean[j] + g * dl[j];
-        h->pool_W = Wn;
+        for (int j = 0; j < d; ++j) h->pool.mean[j] = h->pool.mean[j] + g * dl[j];
+        h->pool.W = Wn;
     }
 }
 
 static void pooled_restart(mcmcx_engine *h)             // chainwsum = initcmatn, chaincmat = cmat0, chainmean = par0
 {
     const int d = h->d;
-    h->pool_W = (double)h->cfg.initcmatn;
-    for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) h->pool_C[h_pidx(i, j, d)] = h->cmat0[(size_t)i + (size_t)j * d];
-    h->pool_mean = h->par0;
+    h->pool.W = (double)h->cfg.initcmatn;
+    for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) h->pool.C[h_pidx(i, j, d)] = h->cmat0[(size_t)i + (size_t)j * d];
+    h->pool.mean = h->par0;
 }
 
 // Pooled tick: the multi-chain form of MCMC_adapt (MCMC_adapt.F90:60-170).  The N current states of all ranks are a
@@ -243,16 +286,9 @@ static int pooled_tick(mcmcx_engine *h, int it, int mode)
     if (mode & AD_BURN) {
         int rc = pooled_reduce(h, 1, it, v); if (rc) return rc;
         const double staypc = v[pooled_vec_len(h, 1) - 1] / (v[0] * (double)it);
-        const double sf = c.scalefactor;
         if (staypc > 1.0 - c.scalelimit || staypc < c.scalelimit) {
-            const bool down = staypc > 1.0 - c.scalelimit;
-            for (auto &r : (h->usesvd ? h->pool_Rf : h->pool_R)) r = down ? r / sf : r * sf;
-            if (h->dodr) {                                  // R2 and iC are scaled themselves (MCMC_adapt.F90:66-78), not recomputed
-                for (auto &r : h->pool_R2) r = down ? r / sf : r * sf;
-                for (auto &r : h->pool_iC) r = down ? r * sf * sf : r / sf / sf;
-            }
-            int rc2 = pooled_upload_R(h);
-            return rc2 ? rc2 : pooled_upload_dr(h, false);
+            pooled_scale(h, staypc > 1.0 - c.scalelimit);
+            return pooled_upload(h);
         }
         if (c.greedy != 0) { pooled_restart(h); pooled_merge(h, v, false); }
         return pooled_factor(h);
@@ -284,19 +320,19 @@ static int pooled_ram_tick(mcmcx_engine *h, int it)
         for (int j = 0; j < d; ++j)
             for (int i = 0; i <= j; ++i) {
                 double acc = 0.0;
-                for (int k = 0; k < d; ++k) acc = std::fma(h->pool_Rf[(size_t)k * d + i], h->pool_Rf[(size_t)k * d + j], acc);
+                for (int k = 0; k < d; ++k) acc = std::fma(h->pool.Rf[(size_t)k * d + i], h->pool.Rf[(size_t)k * d + j], acc);
                 S[(size_t)i + (size_t)j * d] = acc + v[2 + j * (j + 1) / 2 + i] / n;
             }
-        if (host_initial_svd(d, S, h->cfg.condmax, false, Rf, sd, nullptr, false) != 0) { h->pool_status |= ST_CHOL_FAIL; return 0; }
-        h->pool_Rf = Rf;
-        h->pool_alpha = v[1] / n;
-        return pooled_upload_R(h);
+        if (host_initial_svd(d, S, h->cfg.condmax, false, Rf, sd, nullptr, false) != 0) { h->pool.status |= ST_CHOL_FAIL; return 0; }
+        h->pool.Rf = Rf;
+        h->pool.alpha = v[1] / n;
+        return pooled_upload(h);
     }
     std::vector<double> S(P), A;
     for (int j = 0; j < d; ++j)
         for (int i = 0; i <= j; ++i) {
             double acc = 0.0;
-            for (int k = 0; k <= i; ++k) acc = std::fma(h->pool_R[h_pidx(k, i, d)], h->pool_R[h_pidx(k, j, d)], acc);
+            for (int k = 0; k <= i; ++k) acc = std::fma(h->pool.R[h_pidx(k, i, d)], h->pool.R[h_pidx(k, j, d)], acc);
             S[h_pidx(i, j, d)] = acc + v[2 + j * (j + 1) / 2 + i] / n;
         }
     A = S;
@@ -304,7 +340,7 @@ static int pooled_ram_tick(mcmcx_engine *h, int it)
         double dot = 0.0;
         for (int i = 0; i < j; ++i) dot = std::fma(A[h_pidx(i, j, d)], A[h_pidx(i, j, d)], dot);
         double ajj = A[h_pidx(j, j, d)] - dot;
-        if (!(ajj > 0.0)) { h->pool_status |= ST_CHOL_FAIL; return 0; }
+        if (!(ajj > 0.0)) { h->pool.status |= ST_CHOL_FAIL; return 0; }
         double rj = std::sqrt(ajj);
         A[h_pidx(j, j, d)] = rj;
         double rinv = 1.0 / rj;
@@ -314,7 +350,7 @@ static int pooled_ram_tick(mcmcx_engine *h, int it)
             A[h_pidx(j, k, d)] = (A[h_pidx(j, k, d)] - t) * rinv;
         }
     }
-    h->pool_R = A;
-    h->pool_alpha = v[1] / n;
-    return pooled_upload_R(h);
+    h->pool.R = A;
+    h->pool.alpha = v[1] / n;
+    return pooled_upload(h);
 }

@@ -444,7 +444,7 @@ def _factor(oracle, st, d):
     if oracle.lib().mcxo_potrf_u(d, A.ctypes.data_as(C.POINTER(C.c_double))) == 0:
         sq = math.sqrt(float(d))
         st["R"] = np.array([[A[i, j] * 2.4 / sq if i <= j else 0.0 for j in range(d)] for i in range(d)])
-        if st.get("drscale", 0.0) > 0.0:                 # pooled_upload_dr: R2 = R / drscale, iC = dpotri('U', R)
+        if st.get("drscale", 0.0) > 0.0:                 # pooled_dr_fresh: R2 = R / drscale, iC = dpotri('U', R)
             st["R2"] = st["R"] / st["drscale"]
             B = np.asfortranarray(st["R"].copy())
             assert oracle.lib().mcxo_potri_u(d, B.ctypes.data_as(C.POINTER(C.c_double))) == 0
