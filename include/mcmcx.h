@@ -60,7 +60,11 @@ typedef struct mcmcx_config {
     int32_t record_chain;  /* keep every accepted row (the reference's chain/sschain/s2chain) */
     int32_t device;        /* HIP device ordinal */
     int32_t pooled;        /* 1: one proposal factor shared by all chains, adapted from the pooled empirical
-                            * covariance of the current states (multi-chain extension; 0 = the reference's per-chain AM) */
+                            * covariance of the current states (multi-chain extension; 0 = the reference's per-chain AM).
+                            * Every target takes it -- the built-in ones, a target module (mcmcx_set_target_module) and host
+                            * callbacks (mcmcx_set_target_host / _host_batch / _host_er), nycol > 1 included -- except
+                            * mcmcx_set_target_external (-8) and method = 'scam' on the response-column target (-8 / -36);
+                            * no chain holds a factor of its own then */
     int32_t scam_fast;     /* method = 'scam' only, opt-in (default 0 = the reference's operations): the componentwise proposal
                             * newpar = U (U'oldpar + delta e_j) (MCMC_run_scam.F90:106-115: two dgemv) is formed as
                             * newpar = oldpar + delta U(:,j) -- the same point up to the rounding of U U' = I, one column
@@ -82,7 +86,11 @@ int mcmcx_device_info(int32_t device, char *buf, int32_t len); /* "name arch, pc
 int mcmcx_device_ident(int32_t device, char *uuid_hex, int32_t len, int32_t *out5);
 const char *mcmcx_last_kernel(mcmcx_handle h);                /* the sampling kernel the last mcmcx_run launched, as spelled in the
                                                                   source ("step_kernel<true, false, false>", "scam_pooled_kernel", ...);
-                                                                  "" before the first run or with host callbacks (diagnostics) */
+                                                                  "" before the first run or with per-chain factors and the
+                                                                  iteration cut at a user module's / host callbacks' evaluations;
+                                                                  pooled mode names its phase form there ("pooled_phase_kernel",
+                                                                  "pooled_phase_mfma_kernel", "host_phase_kernel<pooled scam>")
+                                                                  (diagnostics) */
 
 int mcmcx_set_par0(mcmcx_handle h, const double *par0, int32_t npar);
 int mcmcx_set_cmat0(mcmcx_handle h, const double *cmat0_colmajor, int32_t npar);
@@ -99,7 +107,8 @@ int mcmcx_set_target_expdata_cols(mcmcx_handle h, int32_t ndata, int32_t nycol, 
  * signatures (the Fortran shim adapts the array-result / assumed-shape ABIs).  The engine calls them from the
  * thread that calls mcmcx_run, one chain after the other, at the points the reference does (MCMC_run.F90:47,55-56,
  * 69,74-75); the candidates make a D2H/H2D round trip per stage, so this is the plumbing path, not the fast one.
- * priorfun / checkbounds may be NULL (flat prior, no bounds = the library defaults). */
+ * priorfun / checkbounds may be NULL (flat prior, no bounds = the library defaults).  With cfg.pooled = 1 the proposals
+ * come from the one shared factor; the callbacks are called exactly as without it. */
 typedef void    (*mcmcx_ssfun_t)(const double *theta, int32_t npar, int32_t ny, double *ss_out, void *user);
 typedef double  (*mcmcx_priorfun_t)(const double *theta, int32_t npar, void *user);
 typedef int32_t (*mcmcx_checkbounds_t)(const double *theta, int32_t npar, void *user);
@@ -108,14 +117,17 @@ int mcmcx_set_target_host(mcmcx_handle h, mcmcx_ssfun_t ss, mcmcx_priorfun_t pri
  * call -- theta[n][npar] row-major (= Fortran theta(npar,n)), ss[n][ny] -- and, with nthreads > 1, is called from that
  * many threads at once on disjoint slices, so it must be re-entrant (the very first evaluation, at mcmcx_init, is made
  * from the calling thread alone, so load-on-first-call code is safe).  Bounds and prior stay per chain on the calling
- * thread, before the batch.  (method = 'er' with mcmcx_set_target_host_er keeps the per-chain path.) */
+ * thread, before the batch.  (method = 'er' with mcmcx_set_target_host_er keeps the per-chain path.)  cfg.pooled = 1: as
+ * for mcmcx_set_target_host. */
 typedef void (*mcmcx_ssfun_batch_t)(const double *theta, int32_t npar, int32_t n, int32_t ny, double *ss_out, void *user);
 int mcmcx_set_target_host_batch(mcmcx_handle h, mcmcx_ssfun_batch_t ss_batch, mcmcx_priorfun_t pri, mcmcx_checkbounds_t cb,
                                 void *user, int32_t nthreads);
 /* The user's ssfunction / priorfun / checkbounds as DEVICE code: a code object (hipcc --genco) whose kernel
  * `kernel_name` was defined with MCMCX_DEFINE_TARGET (include/mcmcx_target.h).  The engine launches it where the
  * reference calls the functions; candidates and results never leave HBM.  userdata (nbytes, may be NULL) is copied
- * to the device and handed to the functions. */
+ * to the device and handed to the functions.  With cfg.pooled = 1 the engine's share of an iteration reads the one
+ * shared factor (npar <= 64: the proposal's product on the matrix cores where that is the faster form) and no chain
+ * holds a factor of its own; several GPUs: mcmcx_set_comm + mcmcx_run_all, or the mcmcx_set_exchange hook. */
 int mcmcx_set_target_module(mcmcx_handle h, const char *code_object_path, const char *kernel_name, const void *userdata, int64_t nbytes);
 /* method='er' with host callbacks: the user's ssfunction_er(theta,npar,ny,sscrit) (external_inc.h:16-20), which may
  * stop summing once it passes sscrit; NULL (default) = ssfunction, like ssfunction_er0.f90.  Same `user` pointer. */

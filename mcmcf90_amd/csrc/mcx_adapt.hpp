@@ -1,6 +1,6 @@
 // mcx_adapt.hpp -- the first point (init_kernel) and MCMC_adapt at a tick (MCMC_adapt.F90:12-230): schedule, covmat in 10 x 10 blocks,
 // MCMC_calculate_R (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam,
-// mcx_pooled, mcx_phase, mcx_adapt, mcx_svd, mcx_moments)
+// mcx_pooled, mcx_phase, mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_phase.hpp"
 

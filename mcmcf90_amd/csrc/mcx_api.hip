@@ -294,7 +294,8 @@ int mcmcx_set_priors(mcmcx_handle h, const double *mu, const double *sig)
 
 // ---- mcmcx_init in steps.  What needs no device memory comes first, so that an invalid configuration allocates nothing; where one
 // trips several checks the code that wins is, in this order: -30, -36, -31 (init_check), then -- the plan made -- the pooled -36, -32,
-// the two pooled -8, -34 and the external-target -8 (initial_factor).
+// the two pooled -8, -34 and the external-target -8 (initial_factor).  The external target is checked first of these: it is a host target
+// without callbacks, and nothing of what follows is meant for it.
 struct InitialFactor { std::vector<double> Rp, Cp, Rfull, qstd, iCp, R2p; };  // R(cmat0), cmat0 packed; the SVD factor; DR: dpotri(R), R2
 static int init_check(mcmcx_engine *h)
 {
@@ -321,8 +322,11 @@ static int initial_factor(mcmcx_engine *h, InitialFactor &f)
 {
     const mcmcx_config &c = h->cfg;
     const int d = h->d, P = h->P;
-    if (h->ny > 1 && h->pooled && (!h->plan.fused_cols || c.method == MCMCX_METHOD_SCAM))
-        return fail(-36, "nycol > 1 in pooled mode: the device-resident response-column target only, and not with method = 'scam'");
+    if (h->external && h->pooled) return fail(-8, "mcmcx_set_target_external: not in pooled mode (the caller drives one evaluation at a "
+        "time; pooled mode takes a target module, mcmcx_set_target_module, or host callbacks, mcmcx_set_target_host)");
+    // (a target module or host callbacks: every method, SCAM through the replicated rotation)
+    if (h->ny > 1 && h->pooled && h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM)
+        return fail(-36, "nycol > 1 in pooled mode: not with method = 'scam' on the device-resident response-column target");
     int info = host_initial_R(d, h->cmat0, f.Rp, f.Cp);
     if (h->usesvd) {                                                                  // Cp (packed cmat0) is still needed
         if (info != 0) { f.Rp.assign(P, 0.0); info = 0; }
@@ -331,15 +335,14 @@ static int initial_factor(mcmcx_engine *h, InitialFactor &f)
     if (info != 0) return fail(-32, "could not factor the initial covariance");      // MCMC_init.F90:110
     if (h->pooled && (long long)c.nchains * (h->comm ? h->comm->nranks : 1) < 2)
         return fail(-8, "pooled mode needs at least 2 chains over all ranks");
-    if (h->pooled && (phase_cut(h) || (h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM)))
-        return fail(-8, "pooled mode needs one of the single-launch device targets (gauss, banana, expdata, expcols; scam: not expcols)");
+    if (h->pooled && h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM)
+        return fail(-8, "pooled mode with method = 'scam': not on the device-resident response-column target (expcols)");
     if (h->dodr) {                                      // iC = dpotri(R), R2 = R/drscale, MCMC_adapt.F90:216-225
         f.iCp = f.Rp; f.R2p.resize(P);
         if (h->usesvd) for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) f.iCp[h_pidx(i, j, d)] = f.Rfull[(size_t)j * d + i];
         if (host_potri(d, f.iCp) != 0) return fail(-34, "ERROR: cannot invert cmat");
         for (int e = 0; e < P; ++e) f.R2p[e] = f.Rp[e] / c.drscale;
     }
-    if (h->external && h->pooled) return fail(-8, "mcmcx_set_target_external: not in pooled mode");
     return 0;
 }
 static int init_engine_dev(mcmcx_engine *h, const InitialFactor &f)    // EngineDev's scalars, the target's and the problem's tables
@@ -1053,6 +1056,10 @@ int mcmcx_run_all(mcmcx_handle *hs, int32_t n, int32_t upto)
     for (int i = 0; i < n; ++i) { if (!hs[i]) return fail(-1, "null handle"); if (phased(hs[i]) && hs[i]->tkind == TGT_HOST) serial = true;
         }
     if (serial) {
+        // (engines that meet in a communicator's ticks cannot run one after the other: the first would wait for the rest in its first tick)
+        for (int i = 0; n > 1 && i < n; ++i) if (collective_run(hs[i])) return fail(-8, "mcmcx_run_all: pooled mode over a communicator "
+            "with host callbacks needs one process per GPU (the callbacks run on the calling thread, one engine after the other); with a target "
+            "module every engine has a thread of its own");
         int worst = 0;
         for (int i = 0; i < n; ++i) { int rc = mcmcx_run(hs[i], upto); if (rc < 0) return rc; worst = std::max(worst, rc); }
         return worst;
@@ -1072,15 +1079,16 @@ int mcmcx_run_all(mcmcx_handle *hs, int32_t n, int32_t upto)
 
 extern "C" {
 // ------------------------------------------------------------------ debug probes (tests only)
-// The kernel-selection tables (launch_step / launch_group / launch_scam): entry `index` as "family:name" into buf; returns the number of
+// The kernel-selection tables (launch_step / launch_group / launch_scam, pooled mode's phase forms): entry `index` as "family:name" into
+// buf; returns the number of
 // entries (so index = -1 with buf = NULL just counts).  Needs no device.
 int mcmcx_debug_kernel_table(int32_t index, char *buf, int32_t len)
 {
-    const KernelEntry *tabs[] = {STEP_TABLE, GROUP_TABLE, SCAM_TABLE};
+    const KernelEntry *tabs[] = {STEP_TABLE, GROUP_TABLE, SCAM_TABLE, PHASE_TABLE};
     const size_t ns[] = {sizeof(STEP_TABLE) / sizeof(STEP_TABLE[0]), sizeof(GROUP_TABLE) / sizeof(GROUP_TABLE[0]),
-        sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0])};
+        sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]), sizeof(PHASE_TABLE) / sizeof(PHASE_TABLE[0])};
     int total = 0, k = index;
-    for (int t = 0; t < 3; ++t) {
+    for (int t = 0; t < 4; ++t) {
         if (k >= 0 && k < (int)ns[t] && buf && len > 0) { snprintf(buf, (size_t)len, "%s:%s", tabs[t][k].family, tabs[t][k].name);
             k = -1 - total - (int)ns[t]; }
         else if (k >= 0) k -= (int)ns[t];

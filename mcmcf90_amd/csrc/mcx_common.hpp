@@ -1,7 +1,7 @@
 // mcx_common.hpp -- what every kernel family shares: the engine's device view (EngineDev), the tile-interleaved layout (TIDX, GV ...),
 // the device-resident targets (ssfunction / priorfun / checkbounds), the normal generator (normal_bm, mcmcrand.F90:166-190)
 // (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam, mcx_pooled, mcx_phase,
-// mcx_adapt, mcx_svd, mcx_moments)
+// mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_device.hpp"
 #include <type_traits>

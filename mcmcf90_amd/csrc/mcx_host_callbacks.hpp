@@ -105,6 +105,62 @@ static int host_eval(mcmcx_engine *h, const double *dev_src, int stride_k, bool 
     return 0;
 }
 
+// ---- pooled mode: the phases of MCMC_run / MCMC_run_er with the shared tables (the plan's form: PooledState layouts, KernelPlan::shared)
+template <int PA, int PB>
+static void launch_pooled_lane(mcmcx_engine *h, int itA)
+{
+    hipLaunchKernelGGL((pooled_phase_kernel<PA, PB>), dim3(h->ntiles), dim3(64), PA == 2 ? lds_step(h) : 0, h->stream, h->E, itA, itA + 1,
+        (const double *)h->d_ramscale, (const double *)h->E.sharedR, (const double *)h->pool.d_R2, (const double *)h->pool.d_iC);
+}
+// PA < 0: iteration itB's proposal alone
+template <int PA, bool STAGE2>
+static void launch_pooled_mfma(mcmcx_engine *h, int itA, int itB)
+{
+    const size_t lds = std::max((size_t)((h->d + 3) & ~3) * 64 * sizeof(double), PA == 2 ? lds_step(h) : (size_t)0);
+    hipLaunchKernelGGL((pooled_phase_mfma_kernel<PA, STAGE2>), dim3(h->ntiles), dim3(64), lds, h->stream, h->E, itA, itB,
+        (const double *)h->d_ramscale, (const double *)(STAGE2 ? h->pool.d_R2T : h->pool.d_RT), (const double *)h->pool.d_iC,
+        h->cfg.method == MCMCX_METHOD_RAM ? 1 : 0);
+}
+// an iteration's last phase PA, with iteration it + 1's proposal behind it when `next`
+template <int PA>
+static void launch_pooled_last(mcmcx_engine *h, int it, bool next)
+{
+    if (!next) launch_pooled_lane<PA, -1>(h, it);                    // (no product in it: the lane kernel in either form)
+    else if (h->plan.pooled_phase == 2) launch_pooled_mfma<PA, false>(h, it, it + 1);
+    else launch_pooled_lane<PA, 0>(h, it);
+    h->p0_done = next;
+}
+static int pooled_host_iteration(mcmcx_engine *h, int it, bool fuse_next)
+{
+    const bool mf = h->plan.pooled_phase == 2;
+    h->last_kernel = h->plan.step->name;
+    if (!h->p0_done) {
+        if (mf) launch_pooled_mfma<-1, false>(h, it, it); else launch_pooled_lane<0, -1>(h, it);
+        HIPCHK(hipGetLastError());
+    }
+    h->p0_done = false;
+    if (h->cfg.method == MCMCX_METHOD_ER) {
+        int rc = host_eval(h, h->E.cand, h->d, false, 1); if (rc) return rc;
+        launch_pooled_lane<3, -1>(h, it);
+        HIPCHK(hipGetLastError());
+        if ((rc = host_eval(h, h->E.cand, h->d, true, 2))) return rc;
+        launch_pooled_last<4>(h, it, fuse_next);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    int rc = host_eval(h, h->E.cand, h->d, false); if (rc) return rc;
+    if (!h->dodr) launch_pooled_last<1>(h, it, fuse_next);
+    else if (mf) launch_pooled_mfma<1, true>(h, it, it);
+    else launch_pooled_lane<1, -1>(h, it);
+    HIPCHK(hipGetLastError());
+    if (h->dodr) {
+        if ((rc = host_eval(h, h->E.cs, 2 * h->d, true))) return rc;
+        launch_pooled_last<2>(h, it, fuse_next);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
 // fuse_next: iteration it + 1 follows without a tick in between -- its proposal (phase 0; SCAM: component 0's phase 5) rides in this
 // iteration's last launch, and h->p0_done tells the next call so (MCMCX_HOST_FUSE=0: one launch per phase, the A/B form the tests compare
 // with)
@@ -115,6 +171,8 @@ static int host_iteration(mcmcx_engine *h, int it, bool fuse_next)
     const size_t lds = lds_step(h);
     const bool fuse = h->plan.host_fuse;
     fuse_next = fuse_next && fuse;
+    if (h->plan.pooled_phase) return pooled_host_iteration(h, it, fuse_next);
+    if (h->pooled) h->last_kernel = h->plan.scam->name;  // (SCAM: the per-chain phases below on every chain's copy of the shared rotation)
     const bool p0_done = h->p0_done;
     h->p0_done = false;
     if (h->cfg.method == MCMCX_METHOD_SCAM) {           // MCMC_run_scam: npar componentwise proposals, each evaluated by the host

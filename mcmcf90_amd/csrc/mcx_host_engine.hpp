@@ -25,7 +25,8 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 struct mcx_switches {
     int pooled_mfma_dr_min = -1, pooled_scalar = -1, dr_big = -1, scam_pooled_16 = -1, scam_fast_lanes = -1, scam_waves = -1,
         svd_lane = -1, cov_batch_rows = -1, ram_wide = -1, pooled_waves = -1, pooled_ks = -1, cols_phased = -1, host_mapped = -1,
-            host_fuse = -1, lds_scratch = -1, group = -1, group_dr2 = -1, group_gw = -1, ram_group = -1, tile_factor = -1;
+            host_fuse = -1, lds_scratch = -1, group = -1, group_dr2 = -1, group_gw = -1, ram_group = -1, tile_factor = -1,
+            pooled_phase_mfma = -1;
     static int get(const char *name) { const char *e = getenv(name); return e ? atoi(e) : -1; }
     void read()
     {
@@ -36,6 +37,7 @@ struct mcx_switches {
         cols_phased = get("MCMCX_COLS_PHASED"); host_mapped = get("MCMCX_HOST_MAPPED"); host_fuse = get("MCMCX_HOST_FUSE");
         lds_scratch = get("MCMCX_LDS_SCRATCH"); group = get("MCMCX_GROUP"); group_dr2 = get("MCMCX_GROUP_DR2");
         group_gw = get("MCMCX_GROUP_GW"); ram_group = get("MCMCX_RAM_GROUP"); tile_factor = get("MCMCX_TILE_FACTOR");
+        pooled_phase_mfma = get("MCMCX_POOLED_PHASE_MFMA");
     }
 };
 // the plain lane step's LDS form (EngineDev::lds_scratch): nothing, the state and scratch vectors (step_kernel_ldsv), those and the packed
@@ -58,7 +60,8 @@ struct KernelPlan {
     bool tile_factor = false;           // the adaptation's Cholesky branch through tile_factor_kernel (npar <= 64)
     bool svd_blocked = false;           // the adaptation's SVD one workgroup per chain (svd_blocked_kernel and its sweeps)
     bool cov_batch = true;              // the covariance's batch branch in blocks (adapt_covb_*) where it applies
-    bool scam_replicated = false;       // pooled SCAM above npar 240: the shared rotation copied to every chain, the per-chain kernels run
+    // pooled SCAM above npar 240 or with a user target: the shared rotation copied to every chain, the per-chain kernels / phases run
+    bool scam_replicated = false;
     // host callbacks with few chains: the exchange vectors in page-locked host memory the device reads and writes directly (no copies
     // between the phases)
     bool host_mapped = false, cs_mapped = false;
@@ -67,6 +70,10 @@ struct KernelPlan {
     bool pooled_mfma = false;           // pooled mode on the matrix cores (pooled_mfma_kernel and kin)
     bool pooled_dr_mfma = false;        // ... with delayed rejection: the dense R2 / iC tables (pooled_mfma_kernel<true>)
     bool pooled_two_waves = false, pooled_forty_rows = false;
+    // pooled mode with the iteration cut at the user's evaluations (a target module, host callbacks): 0 = not, 1 = pooled_phase_kernel
+    // (lane form), 2 = pooled_phase_mfma_kernel (the proposals on the matrix cores); SCAM runs the per-chain phases on the replicated
+    // rotation
+    int pooled_phase = 0;
     bool ram_wide = false;              // method = 'ram' above RAM_SMALL_MAX through step_kernel_ram_wide
     bool scam_pooled12 = false, scam_fast_tile = false; int scam_waves = 1;
     bool am = false;                    // the per-chain adaptation (not RAM, not pooled): covariance, mean and factor scratch per chain
@@ -97,7 +104,8 @@ struct mcmcx_engine {
     int dodr = 0, usesvd = 0;
     bool inited = false;
     int simuind = 0;
-    const char *last_kernel = "";       // name of the sampling kernel launch_step / launch_scam ran last (mcmcx_last_kernel)
+    // name of the sampling kernel launch_step / launch_scam ran last, or of pooled mode's phase form (mcmcx_last_kernel)
+    const char *last_kernel = "";
     std::string launch_err;             // set by a launcher that found no kernel for the configuration: the run fails with it
     // host copies of the problem
     std::vector<double> par0, cmat0;                 // cmat0 col-major d*d

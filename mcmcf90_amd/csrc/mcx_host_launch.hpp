@@ -65,7 +65,7 @@ struct KernelEntry {
     const char *family;                                   // "step" (launch_step), "group" (launch_group), "scam" (launch_scam)
     const char *name;
     bool (*when)(const mcmcx_engine *);
-    void (*launch)(mcmcx_engine *, int it0, int it1);
+    void (*launch)(mcmcx_engine *, int it0, int it1);  // (nullptr: PHASE_TABLE -- host_iteration launches the phases)
     unsigned shared = 0;                                  // pooled mode: the SharedLayout bits its kernel reads (SH_R: E.sharedR's factor)
 };
 static const KernelEntry *pick_entry(const mcmcx_engine *h, const KernelEntry *tab, size_t n)
@@ -450,6 +450,29 @@ static const KernelEntry SCAM_TABLE[] = {
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_kernel, G1, 0, STEP_ARGS, STEP_TGT); }, SH_UREP},
 };
 static void launch_scam(mcmcx_engine *h, int it0, int it1) { launch_entry(h, h->plan.scam, "scam", it0, it1); }
+// ---- pooled mode with the iteration cut at the USER's evaluations (a target module's kernel or host callbacks between the engine's
+// launches): no launcher runs a segment, host_iteration (mcx_host_callbacks.hpp) launches the phases one by one in the form the plan names
+// here, and notes the entry's name for mcmcx_last_kernel.  The entries exist for that name and for the shared layouts they declare.
+// The matrix-core form covers what one pass of four output blocks does (npar <= 64, the largest a target module is compiled for by
+// default); its second stage reads the dense R2 (SH_DRT) and, for the two quadratic forms, the packed inverse covariance (SH_DR).
+static const int POOLED_PHASE_MFMA_MAX_NPAR = 64;
+// ... and where it wins: tools/pooled_phase_sweep.py (profiles/r08_a/phase_form_sweep.txt), the test module's iteration in both forms over
+// npar 10 / 20 / 50 / 64 and 1024 / 65536 / 1048576 chains, user kernel and ticks included: everywhere measured -- lane / mfma 1.18 .. 1.29
+// at npar 10, 1.21 .. 1.38 at 20, 1.37 .. 1.63 at 50, 1.25 .. 1.72 at 64 without delayed rejection, 1.07 .. 1.27 with it (its two quadratic
+// forms stay on the scalar cache in both).  No crossover inside that range: the lane form keeps what was not measured, npar < 10, and
+// what the one-pass product does not cover.  MCMCX_POOLED_PHASE_MFMA = 1 / 0 forces either form where both cover (A/B, tests).
+static bool pooled_phase_mfma(const mcmcx_engine *h, const mcx_switches &sw)
+{
+    if (h->d > POOLED_PHASE_MFMA_MAX_NPAR) return false;
+    if (sw.pooled_phase_mfma == 0 || sw.pooled_phase_mfma == 1) return sw.pooled_phase_mfma == 1;
+    return h->d >= 10;
+}
+static const KernelEntry PHASE_TABLE[] = {
+    {"scam", "host_phase_kernel<pooled scam>", [](const mcmcx_engine *h) { return h->cfg.method == MCMCX_METHOD_SCAM; }, nullptr, SH_UREP},
+    {"step", "pooled_phase_mfma_kernel", [](const mcmcx_engine *h) { return h->plan.pooled_phase == 2; }, nullptr,
+        SH_RT | SH_DRT | SH_DR},
+    {"step", "pooled_phase_kernel", [](const mcmcx_engine *h) { return h->plan.pooled_phase == 1; }, nullptr, SH_R | SH_DR},
+};
 // the adaptation's SVD one workgroup per chain (mcx_svd.hpp) where its rings and row groups are instantiated
 static bool svd_blocked(const mcmcx_engine *h, const mcx_switches &sw)
 {
@@ -470,8 +493,15 @@ static void plan_kernels(mcmcx_engine *h)
     const mcmcx_config &c = h->cfg;
     const int d = h->d, P = h->P, T = h->ntiles;
     const bool am = p.am = (c.method != MCMCX_METHOD_RAM) && (c.doadapt != 0 || c.doburnin != 0) && !h->pooled;
+    // the response-column target: the phases fused into one launch per segment (step_kernel_cols); MCMCX_COLS_PHASED=1 keeps the
+    // separate launches (A/B, tests)
+    p.fused_cols = h->tkind == TGT_EXPCOLS && !(sw.cols_phased > 0);
+    // pooled mode with a user module or host callbacks: the phase launches read the shared tables (SCAM: every chain's copy of the
+    // rotation)
+    const bool pphase = h->pooled && phase_cut(h);
+    if (pphase && c.method != MCMCX_METHOD_SCAM) p.pooled_phase = pooled_phase_mfma(h, sw) ? 2 : 1;
     // step_kernel_pooled_dr_big's and pooled_mfma_kernel<true>'s quadratic-form vectors; npar > 320: adapt_post_kernel's work vector
-    p.xscr = (h->pooled && h->dodr) || d > 320;
+    p.xscr = (h->pooled && h->dodr && !pphase) || d > 320;
     p.dr_lds = h->dodr && dr_fits_lds(h);
     p.dr_vectors_in_lds = dr_vectors_in_lds(h, sw, h->pooled ? 4 : 8);
     {   // plain AM / Metropolis / ER step kernel: state and scratch vectors in LDS (4 d x 512 bytes per wave) when that costs no
@@ -503,12 +533,9 @@ static void plan_kernels(mcmcx_engine *h)
     p.cs_mapped = p.host_mapped && (c.method == MCMCX_METHOD_DRAM || c.method == MCMCX_METHOD_ER);
     // (MCMCX_HOST_FUSE=0: one launch per phase, the A/B form the tests compare with)
     p.host_fuse = sw.host_fuse != 0;
-    // the response-column target: the phases fused into one launch per segment (step_kernel_cols); MCMCX_COLS_PHASED=1 keeps the
-    // separate launches (A/B, tests)
-    p.fused_cols = h->tkind == TGT_EXPCOLS && !(sw.cols_phased > 0);
-    // pooled SCAM: npar > 240: slower, not refused -- scam_kernel / scam_mw_kernel on per-chain copies
-    p.scam_replicated = h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM && scam_pooled_lds(d) > 160 * 1024;
-    p.pooled_mfma = pooled_use_mfma(h, sw);
+    // pooled SCAM: npar > 240: slower, not refused -- scam_kernel / scam_mw_kernel on per-chain copies; a user target: the per-chain phases
+    p.scam_replicated = h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM && (scam_pooled_lds(d) > 160 * 1024 || pphase);
+    p.pooled_mfma = pooled_use_mfma(h, sw) && !pphase;
     p.pooled_dr_mfma = p.pooled_mfma && h->dodr;                 // the second stage on the matrix cores too
     p.pooled_two_waves = pooled_two_waves(h, sw);
     p.pooled_forty_rows = pooled_forty_rows(h, sw);
@@ -546,7 +573,9 @@ static void plan_kernels(mcmcx_engine *h)
     // (test switch: covmat_rows, the lane form)
     p.cov_batch = !(sw.cov_batch_rows > 0);
     // every predicate's inputs are fixed from here on: the launchers run the entry found now
-    if (c.method == MCMCX_METHOD_SCAM) p.scam = pick_entry(h, SCAM_TABLE, sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]));
+    if (pphase) (c.method == MCMCX_METHOD_SCAM ? p.scam : p.step) = pick_entry(h, PHASE_TABLE,
+        sizeof(PHASE_TABLE) / sizeof(PHASE_TABLE[0]));
+    else if (c.method == MCMCX_METHOD_SCAM) p.scam = pick_entry(h, SCAM_TABLE, sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]));
     else if (p.group_d4) p.step = pick_entry(h, GROUP_TABLE, sizeof(GROUP_TABLE) / sizeof(GROUP_TABLE[0]));
     else p.step = pick_entry(h, STEP_TABLE, sizeof(STEP_TABLE) / sizeof(STEP_TABLE[0]));
     // pooled mode: the shared layouts that entry reads (no R2 / iC without DR; the lane kernels read the SVD factor in the dense layout)

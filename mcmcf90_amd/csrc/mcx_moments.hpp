@@ -1,6 +1,6 @@
 // mcx_moments.hpp -- pooled moments of the current states (the one exchanged vector of the multi-GPU path), the fixed pairwise tree, debug
 // probes (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam, mcx_pooled,
-// mcx_phase, mcx_adapt, mcx_svd, mcx_moments)
+// mcx_phase, mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_svd.hpp"
 

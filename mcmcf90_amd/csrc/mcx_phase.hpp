@@ -1,7 +1,7 @@
 // mcx_phase.hpp -- the iteration cut at the user's evaluations: host_phase_kernel (host callbacks), dev_eval_kernel + step_kernel_cols
 // (device target with response columns, nycol >= 1, in one launch), run1_kernel (MCMC_run1 / MCMC_run1_er)
 // (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam, mcx_pooled, mcx_phase,
-// mcx_adapt, mcx_svd, mcx_moments)
+// mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_pooled.hpp"
 
@@ -122,7 +122,8 @@ __global__ __launch_bounds__(64) void dev_eval_kernel(EngineDev E, const double 
 { dev_eval_body(E, blockIdx.x, threadIdx.x, src, stride_k, use_stage2, what); }
 
 // sR / sR2 / siC: pooled mode's shared factor, second-stage factor and inverse covariance (nullptr: the chain's own)
-template <int PHASE, int MSEL = -1>
+// PROPOSE = false: phase 1 leaves the second stage's normals and proposal to its caller (pooled_phase_mfma_kernel: on the matrix cores)
+template <int PHASE, int MSEL = -1, bool PROPOSE = true>
 MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, const double *__restrict__ ramscale, int aux, double *X,
                              const double *__restrict__ sR = nullptr, const double *__restrict__ sR2 = nullptr,
                                  const double *__restrict__ siC = nullptr)
@@ -165,11 +166,13 @@ MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, con
             const bool m = reject;
             if (m) L.drtries += 1;
             for (int j = 0; j < (ny > 1 ? ny : 0); ++j) GV(ss2v, j) = GV(sshev, j);
+            if constexpr (PROPOSE) {
             gen_normals(L.g, zs_t + (size_t)d * 64, lane, d, m);
             if (sR2) { if (E.usesvd) gemvN_shared(sR2, zs_t + (size_t)d * 64, c2_t, theta_t, lane, d); else trmv_shared(sR2,
                 zs_t + (size_t)d * 64, c2_t, theta_t, lane, d); }
             else if (E.usesvd) gemvN_panels(E.R2f + (size_t)tile * d * d * 64, zs_t + (size_t)d * 64, c2_t, theta_t, lane, d, m);
             else trmv_panels<false>(E.R2 + (size_t)tile * E.P * 64, zs_t + (size_t)d * 64, c2_t, theta_t, lane, d, m);
+            }
             GV(hx, HX_SS2) = ss2; GV(hx, HX_PRI2) = pri2;
             GV(hx, HX_REJECT) = reject ? 1.0 : 0.0; GV(hx, HX_STAGE2) = m ? 1.0 : 0.0;
         } else {

@@ -1,6 +1,6 @@
 // mcx_pooled.hpp -- pooled AM / RAM / ER / DR on the f64 matrix cores (pooled_mfma_kernel): one wave per tile, the shared tables' products
 // as v_mfma_f64_16x16x4_f64 tiles (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step,
-// mcx_scam, mcx_pooled, mcx_phase, mcx_adapt, mcx_svd, mcx_moments)
+// mcx_scam, mcx_pooled, mcx_phase, mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_scam.hpp"
 

@@ -1,7 +1,7 @@
 // mcx_products.hpp -- the matrix-vector products of MCMC_propose (MCMC_DRAM.F90:20-31) on a lane's own factor: dtrmv('U','T') on the packed
 // triangle in column panels, the full-matrix forms of the SVD paths, the lane-per-chain Jacobi SVD, the shared-table (pooled) forms
 // (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam, mcx_pooled, mcx_phase,
-// mcx_adapt, mcx_svd, mcx_moments)
+// mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_common.hpp"
 

@@ -1,7 +1,7 @@
 // mcx_step.hpp -- the lane-per-chain sampling kernels: MCMC_run / MCMC_run_ram / MCMC_run_er iterations (step_body), MCMC_adapt_ram with
 // DCHUD / DCHDD in two sweeps over column panels (ram_update), delayed rejection (dr_body), and their __global__ entry points
 // (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam, mcx_pooled, mcx_phase,
-// mcx_adapt, mcx_svd, mcx_moments)
+// mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_products.hpp"
 

@@ -1,6 +1,6 @@
 // mcx_svd.hpp -- the adaptation's SVD at large npar: blocked one-sided Jacobi (the pinned routine, oracle/mcx_svd.h), one workgroup per
 // chain (one of the family headers mcx_kernels.hpp includes, in this order: mcx_common, mcx_products, mcx_step, mcx_scam, mcx_pooled,
-// mcx_phase, mcx_adapt, mcx_svd, mcx_moments)
+// mcx_phase, mcx_pooled_phase, mcx_adapt, mcx_svd, mcx_moments)
 #pragma once
 #include "mcx_adapt.hpp"
 
