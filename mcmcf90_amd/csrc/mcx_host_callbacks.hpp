@@ -1,5 +1,8 @@
-// mcx_host_callbacks.hpp -- the user's host ssfunction / priorfun / checkbounds between the phase kernels (host_eval, host_iteration); MCMC_run1's exchange vectors.
-// Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch, mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
+// mcx_host_callbacks.hpp -- the iteration cut at the user's evaluations: host_eval (the user's host ssfunction / priorfun / checkbounds, a
+// target module's kernel or the response-column target between the phase kernels), launch_phase (which kernel carries a phase, per chain or
+// in pooled mode's two forms) and host_iteration, the one statement of the protocol; MCMC_run1's exchange vectors.
+// Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch,
+// mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
 // Host-callback evaluation of one candidate vector per chain, in chain order, from the calling thread
 // (the reference's callbacks keep SAVEd state and are not thread-safe: testcases/mcmcrun.F90:69-70).
@@ -40,23 +43,31 @@ static int host_eval(mcmcx_engine *h, const double *dev_src, int stride_k, bool 
     double *h_ev = mapped ? h->E.hev : h->h_ev.data();
     memset(h_ev, 0, L * nhe * sizeof(double));
     std::vector<double> th(d);
-    if (h->h_ss_batch && !(what == 2 && h->h_ss_er)) {
-        // Batched form (opt-in): bounds and prior per chain on this thread, in chain order; then ONE call of the user's
-        // ssfunction_batch per worker thread over the chains that need the sum of squares.
-        h->h_bidx.clear(); h->h_bth.clear();
-        for (int c = 0; c < h->cfg.nchains; ++c) {
-            const int t = c / 64, l = c % 64;
-            if (use_stage2_flag && hx[((size_t)t * NHX + HX_STAGE2) * 64 + l] == 0.0) continue;
-            for (int k = 0; k < d; ++k) th[k] = h_cand[((size_t)t * stride_k + k) * 64 + l];
-            int inb = 1; double pri = 0.0;
-            if (what != 2) {
-                inb = h->h_cb ? h->h_cb(th.data(), d, h->h_user) : 1;
-                if (inb) pri = h->h_pri ? h->h_pri(th.data(), d, h->h_user) : 0.0;
-            }
-            h_ev[((size_t)t * nhe + HE_INB) * 64 + l] = inb ? 1.0 : 0.0;
-            h_ev[((size_t)t * nhe + HE_PRI) * 64 + l] = pri;
-            if ((what == 0 && inb) || what == 2) { h->h_bidx.push_back(c); h->h_bth.insert(h->h_bth.end(), th.begin(), th.end()); }
+    // The chains in order, on this thread: bounds, then the prior where in bounds (MCMC_run.F90:54-56: prior first), then the sum of
+    // squares where it is needed -- at once, or queued for the user's ssfunction_batch (opt-in; ssfunction_er keeps the per-chain call)
+    const bool batch = h->h_ss_batch && !(what == 2 && h->h_ss_er);
+    if (batch) { h->h_bidx.clear(); h->h_bth.clear(); }
+    for (int c = 0; c < h->cfg.nchains; ++c) {
+        const int t = c / 64, l = c % 64;
+        if (use_stage2_flag && hx[((size_t)t * NHX + HX_STAGE2) * 64 + l] == 0.0) continue;
+        for (int k = 0; k < d; ++k) th[k] = h_cand[((size_t)t * stride_k + k) * 64 + l];
+        int inb = 1;
+        double pri = 0.0;
+        if (what != 2) {
+            inb = h->h_cb ? h->h_cb(th.data(), d, h->h_user) : 1;                    // checkbounds0.f90: .true.
+            if (inb) pri = h->h_pri ? h->h_pri(th.data(), d, h->h_user) : 0.0;
         }
+        h_ev[((size_t)t * nhe + HE_INB) * 64 + l] = inb ? 1.0 : 0.0;
+        h_ev[((size_t)t * nhe + HE_PRI) * 64 + l] = pri;
+        if (what == 1 || !inb) continue;                                             // (no sum of squares: its slots stay zero)
+        if (batch) { h->h_bidx.push_back(c); h->h_bth.insert(h->h_bth.end(), th.begin(), th.end()); continue; }
+        std::fill(ssc.begin(), ssc.end(), 0.0);
+        if (what == 2 && h->h_ss_er)                                                 // MCMC_ssfunction_er(newpar, sscrit)
+            h->h_ss_er(th.data(), d, ny, hx[((size_t)t * NHX + HX_CRIT) * 64 + l], ssc.data(), h->h_user);
+        else h->h_ss(th.data(), d, ny, ssc.data(), h->h_user);                       // (ssfunction_er0.f90: no er for ss)
+        for (int j = 0; j < ny; ++j) h_ev[((size_t)t * nhe + HE_SS + j) * 64 + l] = ssc[j];
+    }
+    if (batch) {                                         // ONE call of ssfunction_batch per worker thread over the queued chains
         const int n = (int)h->h_bidx.size();
         h->h_bss.assign((size_t)n * ny, 0.0);
         // the first evaluation (MCMC_init's starting point) stays on the calling thread: user code commonly loads its
@@ -76,36 +87,17 @@ static int host_eval(mcmcx_engine *h, const double *dev_src, int stride_k, bool 
             const int c = h->h_bidx[i], t = c / 64, l = c % 64;
             for (int j = 0; j < ny; ++j) h_ev[((size_t)t * nhe + HE_SS + j) * 64 + l] = h->h_bss[(size_t)i * ny + j];
         }
-        if (!mapped) HIPCHK(hipMemcpyAsync(h->E.hev, h->h_ev.data(), h->h_ev.size() * 8, hipMemcpyHostToDevice, h->stream));
-        return 0;
-    }
-    for (int c = 0; c < h->cfg.nchains; ++c) {
-        const int t = c / 64, l = c % 64;
-        if (use_stage2_flag && hx[((size_t)t * NHX + HX_STAGE2) * 64 + l] == 0.0) continue;
-        for (int k = 0; k < d; ++k) th[k] = h_cand[((size_t)t * stride_k + k) * 64 + l];
-        int inb = 1;
-        double pri = 0.0;
-        std::fill(ssc.begin(), ssc.end(), 0.0);
-        if (what == 2) {                                                             // MCMC_ssfunction_er(newpar, sscrit)
-            const double crit = hx[((size_t)t * NHX + HX_CRIT) * 64 + l];
-            if (h->h_ss_er) h->h_ss_er(th.data(), d, ny, crit, ssc.data(), h->h_user);
-            else h->h_ss(th.data(), d, ny, ssc.data(), h->h_user);                   // ssfunction_er0.f90: no er for ss
-        } else {
-            inb = h->h_cb ? h->h_cb(th.data(), d, h->h_user) : 1;                    // checkbounds0.f90: .true.
-            if (inb) {                                                               // MCMC_run.F90:54-56: prior first
-                pri = h->h_pri ? h->h_pri(th.data(), d, h->h_user) : 0.0;
-                if (what == 0) h->h_ss(th.data(), d, ny, ssc.data(), h->h_user);
-            }
-        }
-        h_ev[((size_t)t * nhe + HE_INB) * 64 + l] = inb ? 1.0 : 0.0;
-        h_ev[((size_t)t * nhe + HE_PRI) * 64 + l] = pri;
-        for (int j = 0; j < ny; ++j) h_ev[((size_t)t * nhe + HE_SS + j) * 64 + l] = ssc[j];
     }
     if (!mapped) HIPCHK(hipMemcpyAsync(h->E.hev, h->h_ev.data(), h->h_ev.size() * 8, hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
-// ---- pooled mode: the phases of MCMC_run / MCMC_run_er with the shared tables (the plan's form: PooledState layouts, KernelPlan::shared)
+// ---- the phase launches.  An iteration cut at the evaluations runs as phases: 0 the proposal, 1 the first stage's decision (with delayed
+// rejection: and the second stage's proposal), 2 the second stage's decision, 3 early rejection's threshold, 4 its decision; SCAM: 5 a
+// component's proposal, 6 its decision, 7 the iteration's end.  Which kernel carries a phase is the plan's business: the per-chain
+// host_phase_kernel / host_phase_seq_kernel, or in pooled mode (KernelPlan::pooled_phase, the shared tables in PooledState's layouts)
+// pooled_phase_kernel / pooled_phase_mfma_kernel.  launch_phase and launch_scam_phase are the only code that knows their argument lists;
+// both leave h->p0_done saying whether iteration it + 1's proposal rode along, and report the launch's error.
 template <int PA, int PB>
 static void launch_pooled_lane(mcmcx_engine *h, int itA)
 {
@@ -121,101 +113,85 @@ static void launch_pooled_mfma(mcmcx_engine *h, int itA, int itB)
         (const double *)h->d_ramscale, (const double *)(STAGE2 ? h->pool.d_R2T : h->pool.d_RT), (const double *)h->pool.d_iC,
         h->cfg.method == MCMCX_METHOD_RAM ? 1 : 0);
 }
-// an iteration's last phase PA, with iteration it + 1's proposal behind it when `next`
-template <int PA>
-static void launch_pooled_last(mcmcx_engine *h, int it, bool next)
+// Phase P (0 .. 4) of iteration it; next: iteration it + 1's proposal behind it in the same launch (P an iteration's last phase: 1, 2, 4).
+// The matrix-core form carries the launches with a proposal in them -- with delayed rejection phase 1's second-stage proposal too --
+// and leaves the others to the lane form; the per-chain kernels take the step size at ramscale + it, the others the table's base.
+template <int P>
+static int launch_phase(mcmcx_engine *h, int it, bool next = false)
 {
-    if (!next) launch_pooled_lane<PA, -1>(h, it);                    // (no product in it: the lane kernel in either form)
-    else if (h->plan.pooled_phase == 2) launch_pooled_mfma<PA, false>(h, it, it + 1);
-    else launch_pooled_lane<PA, 0>(h, it);
-    h->p0_done = next;
-}
-static int pooled_host_iteration(mcmcx_engine *h, int it, bool fuse_next)
-{
-    const bool mf = h->plan.pooled_phase == 2;
-    h->last_kernel = h->plan.step->name;
-    if (!h->p0_done) {
-        if (mf) launch_pooled_mfma<-1, false>(h, it, it); else launch_pooled_lane<0, -1>(h, it);
-        HIPCHK(hipGetLastError());
+    constexpr bool LAST = P == 1 || P == 2 || P == 4;
+    const dim3 g(h->ntiles), b(64);
+    const size_t lds = P == 2 ? lds_step(h) : 0;
+    const double *rs0 = h->d_ramscale;
+    const int form = h->plan.pooled_phase;
+    h->p0_done = LAST && next;
+    if (h->p0_done) {
+        if constexpr (LAST) {
+            if (form == 0) hipLaunchKernelGGL((host_phase_seq_kernel<P, 0, -1>), g, b, lds, h->stream, h->E, it, 0, it + 1, 0, 0, 0, rs0);
+            else if (form == 2) launch_pooled_mfma<P, false>(h, it, it + 1);
+            else launch_pooled_lane<P, 0>(h, it);
+        }
     }
+    else if (form == 0) hipLaunchKernelGGL((host_phase_kernel<P>), g, b, lds, h->stream, h->E, it, rs0 + it, 0);
+    else if (form == 2 && P == 0) launch_pooled_mfma<-1, false>(h, it, it);
+    else if (form == 2 && P == 1 && h->dodr) launch_pooled_mfma<1, true>(h, it, it);
+    else launch_pooled_lane<P, -1>(h, it);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// SCAM's phases of component j, on the per-chain kernels (pooled mode: on every chain's copy of the shared rotation).  A decision (6)
+// carries what no evaluation separates from it: PB = 5 the next component's proposal, PB = 7 the iteration's end and, PC = 5, iteration
+// it + 1's first proposal -- in one launch, or with MCMCX_HOST_FUSE=0 one launch per phase
+template <int PA, int PB = -1, int PC = -1>
+static int launch_scam_phase(mcmcx_engine *h, int it, int j)
+{
+    const dim3 g(h->ntiles), b(64);
+    const double *rs0 = h->d_ramscale;
+    const int auxB = PB == 5 ? j + 1 : 0;
     h->p0_done = false;
-    if (h->cfg.method == MCMCX_METHOD_ER) {
-        int rc = host_eval(h, h->E.cand, h->d, false, 1); if (rc) return rc;
-        launch_pooled_lane<3, -1>(h, it);
-        HIPCHK(hipGetLastError());
-        if ((rc = host_eval(h, h->E.cand, h->d, true, 2))) return rc;
-        launch_pooled_last<4>(h, it, fuse_next);
+    if constexpr (PB >= 0) if (h->plan.host_fuse) {
+        hipLaunchKernelGGL((host_phase_seq_kernel<PA, PB, PC>), g, b, 0, h->stream, h->E, it, j, it, auxB, PC >= 0 ? it + 1 : 0, 0, rs0);
+        h->p0_done = PC >= 0;
         HIPCHK(hipGetLastError());
         return 0;
     }
-    int rc = host_eval(h, h->E.cand, h->d, false); if (rc) return rc;
-    if (!h->dodr) launch_pooled_last<1>(h, it, fuse_next);
-    else if (mf) launch_pooled_mfma<1, true>(h, it, it);
-    else launch_pooled_lane<1, -1>(h, it);
+    hipLaunchKernelGGL((host_phase_kernel<PA>), g, b, 0, h->stream, h->E, it, rs0 + it, j);
     HIPCHK(hipGetLastError());
-    if (h->dodr) {
-        if ((rc = host_eval(h, h->E.cs, 2 * h->d, true))) return rc;
-        launch_pooled_last<2>(h, it, fuse_next);
-        HIPCHK(hipGetLastError());
-    }
+    if constexpr (PB >= 0) { hipLaunchKernelGGL((host_phase_kernel<PB>), g, b, 0, h->stream, h->E, it, rs0 + it, auxB);
+        HIPCHK(hipGetLastError()); }
     return 0;
 }
 
-// fuse_next: iteration it + 1 follows without a tick in between -- its proposal (phase 0; SCAM: component 0's phase 5) rides in this
-// iteration's last launch, and h->p0_done tells the next call so (MCMCX_HOST_FUSE=0: one launch per phase, the A/B form the tests compare
-// with)
+// One iteration of MCMC_run / MCMC_run_er / MCMC_run_scam with the user's evaluations between the phases, in every form of the plan.
+// fuse_next: iteration it + 1 follows without a tick in between -- its proposal rides in this iteration's last launch, and h->p0_done
+// tells the next call so (MCMCX_HOST_FUSE=0: one launch per phase, the A/B form the tests compare with)
 static int host_iteration(mcmcx_engine *h, int it, bool fuse_next)
 {
-    const dim3 g(h->ntiles), b(64);
-    const double *rs = h->d_ramscale + it, *rs0 = h->d_ramscale;
-    const size_t lds = lds_step(h);
-    const bool fuse = h->plan.host_fuse;
-    fuse_next = fuse_next && fuse;
-    if (h->plan.pooled_phase) return pooled_host_iteration(h, it, fuse_next);
-    if (h->pooled) h->last_kernel = h->plan.scam->name;  // (SCAM: the per-chain phases below on every chain's copy of the shared rotation)
+    const int d = h->d;
     const bool p0_done = h->p0_done;
-    h->p0_done = false;
-    if (h->cfg.method == MCMCX_METHOD_SCAM) {           // MCMC_run_scam: npar componentwise proposals, each evaluated by the host
-        for (int j = 0; j < h->d; ++j) {
-            if (!(j == 0 ? p0_done : fuse)) { hipLaunchKernelGGL((host_phase_kernel<5>), g, b, 0, h->stream, h->E, it, rs, j);
-                HIPCHK(hipGetLastError()); }
-            int rc = host_eval(h, h->E.cand, h->d, false); if (rc) return rc;
-            if (!fuse) hipLaunchKernelGGL((host_phase_kernel<6>), g, b, 0, h->stream, h->E, it, rs, j);
-            else if (j + 1 < h->d) hipLaunchKernelGGL((host_phase_seq_kernel<6, 5, -1>), g, b, 0, h->stream, h->E, it, j, it, j + 1, 0, 0,
-                rs0);
-            else if (fuse_next) { hipLaunchKernelGGL((host_phase_seq_kernel<6, 7, 5>), g, b, 0, h->stream, h->E, it, j, it, 0, it + 1, 0,
-                rs0); h->p0_done = true; }
-            else hipLaunchKernelGGL((host_phase_seq_kernel<6, 7, -1>), g, b, 0, h->stream, h->E, it, j, it, 0, 0, 0, rs0);
-            HIPCHK(hipGetLastError());
+    int rc;
+    fuse_next = fuse_next && h->plan.host_fuse;
+    if (h->pooled) h->last_kernel = (h->plan.pooled_phase ? h->plan.step : h->plan.scam)->name;
+    if (h->cfg.method == MCMCX_METHOD_SCAM) {           // MCMC_run_scam: npar componentwise proposals, each evaluated by the user
+        for (int j = 0; j < d; ++j) {
+            if (j == 0 && !p0_done && (rc = launch_scam_phase<5>(h, it, 0))) return rc;
+            if ((rc = host_eval(h, h->E.cand, d, false))) return rc;
+            rc = j + 1 < d ? launch_scam_phase<6, 5>(h, it, j) : fuse_next ? launch_scam_phase<6, 7, 5>(h, it, j)
+                : launch_scam_phase<6, 7>(h, it, j);
+            if (rc) return rc;
         }
-        if (!fuse) { hipLaunchKernelGGL((host_phase_kernel<7>), g, b, 0, h->stream, h->E, it, rs, 0); HIPCHK(hipGetLastError()); }
         return 0;
     }
-    if (!p0_done) { hipLaunchKernelGGL((host_phase_kernel<0>), g, b, 0, h->stream, h->E, it, rs, 0); HIPCHK(hipGetLastError()); }
+    if (!p0_done && (rc = launch_phase<0>(h, it))) return rc;
     if (h->cfg.method == MCMCX_METHOD_ER) {             // MCMC_run_er: the threshold is drawn between priorfun and ssfunction_er
-        int rc = host_eval(h, h->E.cand, h->d, false, 1); if (rc) return rc;
-        hipLaunchKernelGGL((host_phase_kernel<3>), g, b, 0, h->stream, h->E, it, rs, 0);
-        HIPCHK(hipGetLastError());
-        rc = host_eval(h, h->E.cand, h->d, true, 2); if (rc) return rc;
-        if (fuse_next) { hipLaunchKernelGGL((host_phase_seq_kernel<4, 0, -1>), g, b, 0, h->stream, h->E, it, 0, it + 1, 0, 0, 0, rs0);
-            h->p0_done = true; }
-        else hipLaunchKernelGGL((host_phase_kernel<4>), g, b, 0, h->stream, h->E, it, rs, 0);
-        HIPCHK(hipGetLastError());
-        return 0;
+        if ((rc = host_eval(h, h->E.cand, d, false, 1)) || (rc = launch_phase<3>(h, it)) || (rc = host_eval(h, h->E.cand, d, true, 2)))
+            return rc;
+        return launch_phase<4>(h, it, fuse_next);
     }
-    int rc = host_eval(h, h->E.cand, h->d, false); if (rc) return rc;
-    if (fuse_next && !h->dodr) { hipLaunchKernelGGL((host_phase_seq_kernel<1, 0, -1>), g, b, 0, h->stream, h->E, it, 0, it + 1, 0, 0, 0,
-        rs0); h->p0_done = true; }
-    else hipLaunchKernelGGL((host_phase_kernel<1>), g, b, 0, h->stream, h->E, it, rs, 0);
-    HIPCHK(hipGetLastError());
-    if (h->dodr) {
-        rc = host_eval(h, h->E.cs, 2 * h->d, true); if (rc) return rc;
-        if (fuse_next) { hipLaunchKernelGGL((host_phase_seq_kernel<2, 0, -1>), g, b, lds, h->stream, h->E, it, 0, it + 1, 0, 0, 0, rs0);
-            h->p0_done = true; }
-        else hipLaunchKernelGGL((host_phase_kernel<2>), g, b, lds, h->stream, h->E, it, rs, 0);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
+    if ((rc = host_eval(h, h->E.cand, d, false))) return rc;
+    if (!h->dodr) return launch_phase<1>(h, it, fuse_next);
+    if ((rc = launch_phase<1>(h, it)) || (rc = host_eval(h, h->E.cs, 2 * d, true))) return rc;
+    return launch_phase<2>(h, it, fuse_next);
 }
 
 // ---- MCMC_run1 / MCMC_run1_er: the arithmetic of one invocation (run1_kernel), all chains at once, vectors row-major per chain

@@ -482,6 +482,45 @@ static bool svd_blocked(const mcmcx_engine *h, const mcx_switches &sw)
     // (its rings and row groups are instantiated up to npar 256)
     return h->d >= 48 && h->d <= 256;
 }
+// the adaptation tick's forms (AdaptPlan): from npar, the tile count and the plan's tile_factor / svd_blocked
+static void plan_adapt(const mcmcx_engine *h, KernelPlan &p)
+{
+    AdaptPlan &a = p.adapt;
+    const int d = h->d;
+    a.n10 = (d + TD - 1) / TD; a.noff = a.n10 * (a.n10 - 1) / 2;          // blocks of ten (triangular on the diagonal)
+    a.g8 = (unsigned)(8 * ((h->ntiles + 7) / 8));
+    // one d-vector / the Cholesky's diagonal block (18 kB: eight waves per CU up to npar 36)
+    a.post_lds = std::max(lds_bytes(h) / 2, (size_t)36 * 64 * sizeof(double));
+    const bool xg = a.post_lds > 160 * 1024;
+    if (xg) a.post_lds = 0;
+    a.post = h->usesvd ? (xg ? adapt_post_kernel<true, true> : adapt_post_kernel<true, false>)
+                       : (xg ? adapt_post_kernel<false, true> : adapt_post_kernel<false, false>);
+    if (p.tile_factor) {
+        const int nc = (d + 15) / 16, nw = nc <= 2 ? 4 : nc == 3 ? 2 : 1, ch = 4 * nw;
+        a.factor = nc == 1 ? tile_factor_kernel<1, 4> : nc == 2 ? tile_factor_kernel<2, 4> : nc == 3 ? tile_factor_kernel<3, 2>
+            : tile_factor_kernel<4, 1>;
+        a.factor_block = (unsigned)(64 * nw);
+        a.factor_lds = (size_t)ch * (h->P | 1) * sizeof(double) + (size_t)ch * sizeof(int);
+        a.factor_grid = a.g8 * (unsigned)(64 / ch);
+    }
+    if (p.svd_blocked) {
+        if (d <= 200) {
+            const int RL = d <= 64 ? 8 : d <= 128 ? 16 : 25;
+            a.sweep32 = RL == 8 ? svd_sweep_stream32_kernel<8> : RL == 16 ? svd_sweep_stream32_kernel<16> : svd_sweep_stream32_kernel<25>;
+            a.sweep_lds = (size_t)33 * (8 * RL + 2) * sizeof(double);
+        } else {
+            const int RL = d <= 208 ? 26 : 32;
+            a.svd_sb = 24;                               // pair-lanes: whole waves of octets, one wave of loaders at least
+            a.sweep = RL == 26 ? svd_sweep_stream_kernel<26> : svd_sweep_stream_kernel<32>;
+            a.sweep_lds = (size_t)(a.svd_sb + 2) * (8 * RL + 2) * sizeof(double);
+        }
+        const int RP = d <= 64 ? 4 : d <= 128 ? 8 : d <= 208 ? 13 : 16;
+        a.applyv = RP == 4 ? svd_applyv_stream32_kernel<4> : RP == 8 ? svd_applyv_stream32_kernel<8>
+            : RP == 13 ? svd_applyv_stream32_kernel<13> : svd_applyv_stream32_kernel<16>;
+        a.applyv_lds = (size_t)33 * (4 * RP + 6) * sizeof(double);
+        a.applyv_grid = (unsigned)(32 * ((h->nlanes + 7) / 8));            // four one-wave workgroups per chain, a chain's on one XCD
+    }
+}
 // ---- the plan: every kernel form the engine takes, decided once at mcmcx_init before anything is allocated.  Its inputs are the
 // configuration, the problem's shape, the target kind, the switches (read here, nowhere else) and the CU count; never a device pointer.
 static void plan_kernels(mcmcx_engine *h)
@@ -572,6 +611,7 @@ static void plan_kernels(mcmcx_engine *h)
     p.svd_blocked = svd_blocked(h, sw) && (c.doadapt != 0 || c.doburnin != 0);
     // (test switch: covmat_rows, the lane form)
     p.cov_batch = !(sw.cov_batch_rows > 0);
+    plan_adapt(h, p);
     // every predicate's inputs are fixed from here on: the launchers run the entry found now
     if (pphase) (c.method == MCMCX_METHOD_SCAM ? p.scam : p.step) = pick_entry(h, PHASE_TABLE,
         sizeof(PHASE_TABLE) / sizeof(PHASE_TABLE[0]));

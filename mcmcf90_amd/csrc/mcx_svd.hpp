@@ -20,8 +20,8 @@ namespace mcx {
 //     ring of LDS columns (below);
 //   * V is kept OUT of the sweep: it never feeds back into the rotations, so the sweep only logs (c, s) per pair and
 //     svd_applyv_stream32_kernel replays the log on V afterwards, row-parallel and barrier-free (a wave owns its rows).
-// One launch of each per sweep; the host stops when no chain rotated (mcx_api.hip: launch_adapt).  Storage is chain-major here (a chain's
-// column = 8 d contiguous bytes); tile2chain_kernel / chain2tile_kernel convert from and to the engine's tile-interleaved layout.
+// One launch of each per sweep; the host stops when no chain rotated (mcx_host_adapt.hpp: launch_adapt).  Storage is chain-major here (a
+// chain's column = 8 d contiguous bytes); tile2chain_kernel / chain2tile_kernel convert from and to the engine's tile-interleaved layout.
 // Earlier generations of these kernels (block pairs in LDS; the I block in registers without the stream; a shared scalar tail per pair)
 // are bit-equal, slower, and no longer in the library: tools/variants/README.md.
 // LDS column stride: even (16-byte accesses), = 2 mod 4 (16 lanes on 16 columns: 64 banks)

@@ -84,6 +84,49 @@ def test_host_callbacks_equal_device_target(oracle, name, nsimu, plumbing, monke
     e.close()
 
 
+@pytest.mark.parametrize("name", ["e6_expdata_er_priors", "s1_gauss6_scam", "s3_gauss6_dram_svd_dr"])
+@pytest.mark.parametrize("plumbing", ["fused_mapped", "phase_launches_and_copies"])
+def test_host_callbacks_cut_at_a_tick(oracle, name, plumbing, monkeypatch):
+    """Early rejection, SCAM and delayed rejection with an SVD factor through the host callbacks, the run cut into four mcmcx_run calls around
+    an adaptation: at the tick (the proposal must not have ridden ahead of the factor the tick replaces), one iteration after it (that
+    proposal launched alone) and one more (the first that rode in the previous iteration's last launch is handed over between two calls).
+    In both plumbing forms, against the oracle bit for bit.  nsimu = 2 adaptint + 3: past the second tick an iteration of each kind -- the
+    proposal alone, the one that rode ahead, the run's last, which carries none."""
+    if plumbing != "fused_mapped":
+        monkeypatch.setenv("MCMCX_HOST_MAPPED", "0"); monkeypatch.setenv("MCMCX_HOST_FUSE", "0")
+    from mcmcf90_amd import Engine, make_config
+    z, cfg, prob = load(name, oracle)
+    ckw, pkw = _kw(z)
+    t = int(ckw["adaptint"])
+    assert ckw["burnintime"] == 0 and ckw["adapthist"] == 0 and ckw["doadapt"] == 1        # the ticks are at t and 2 t
+    ckw["nsimu"] = 2 * t + 3
+    cfg = oracle.make_cfg(**ckw)
+    L = oracle.lib()
+    tgt = prob.ctarget()
+    L.mcxo_ssfun.restype = C.c_double; L.mcxo_priorfun.restype = C.c_double; L.mcxo_checkbounds.restype = C.c_int
+    dp = C.POINTER(C.c_double)
+    npar, nch = int(pkw["npar"]), 3
+    e = Engine(make_config(npar, nch, record_chain=1, chain_id0=5, **ckw))
+    e.setpar0(pkw["par0"]); e.setcmat0(np.asarray(pkw["cmat0"], dtype=float).reshape(npar, npar))
+    e.setsigma2nobs(float(pkw.get("sigma2", 1.0)), int(pkw.get("nobs", 1)))
+    e.set_target_host(lambda th: L.mcxo_ssfun(C.byref(tgt), th.ctypes.data_as(dp)),
+                      lambda th: L.mcxo_priorfun(C.byref(tgt), th.ctypes.data_as(dp)),
+                      lambda th: bool(L.mcxo_checkbounds(C.byref(tgt), th.ctypes.data_as(dp))))
+    e.init(); e.run(t); e.run(t + 1); e.run(t + 2); e.run()
+    for c in range(nch):
+        o = oracle.run_chain(cfg, prob, chain_id=5 + c)
+        ch, ss, s2 = e.chain(c)
+        np.testing.assert_array_equal(_bits(ch), _bits(o.chain))
+        np.testing.assert_array_equal(_bits(ss), _bits(o.sschain))
+        if cfg.updatesigma:
+            np.testing.assert_array_equal(_bits(s2), _bits(o.s2chain))
+        cnt = e.counters(c)
+        assert (cnt["stayed"], cnt["bndstayed"], cnt["draccepted"], cnt["drtries"], cnt["erstayed"]) == \
+               (o.stayed, o.bndstayed, o.draccepted, o.drtries, o.erstayed)
+        assert e.rng(c)[0] == o.rng_n
+    e.close()
+
+
 @pytest.mark.parametrize("early", [False, True])
 def test_host_callbacks_early_rejection(oracle, early):
     """method='er' through the host callbacks (MCMC_run_er.F90:54-101): checkbounds and priorfun first, the threshold
