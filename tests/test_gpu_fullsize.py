@@ -41,7 +41,12 @@ def test_c2_gauss10_am_65536_chains(oracle):
     pop = int(np.unpackbits(masks.view(np.uint8)).sum())
     assert pop == n * nsimu - tot["stayed"]                   # accepted (incl. row 1) + stayed = nsimu per chain
     assert tot["proposals"] == n * (nsimu - 1)
-    mean, cov = mdist.finalize_moments(e.pooled_moments(), d, np.zeros(d))
+    import moment_tree_ref as mt
+    moments = e.pooled_moments()
+    # 1024 tiles: two launches of the tile tree, bit for bit the documented tree of these very states (a dropped or doubled tile, a wrong pairing)
+    np.testing.assert_array_equal(_bits(moments), _bits(mt.pooled_moments_ref(e.theta(), pkw["par0"])))
+    assert moments[0] == n
+    mean, cov = mdist.finalize_moments(moments, d, np.zeros(d))
     assert np.max(np.abs(mean)) < 0.03                        # N(0, I): se = 1/sqrt(65536) = 0.004
     assert np.max(np.abs(cov - np.eye(d))) < 0.05
     acc = 1.0 - tot["stayed"] / (n * (nsimu - 1.0))

@@ -626,6 +626,50 @@ def test_pooled_burnin_greedy_ap_match_restatement(oracle, name, extra, c0):
     e.close()
 
 
+def _getter_after_tick(e, pkw, msg):
+    """mcmcx_pooled_moments after a run whose last tick reduced a longer vector (kind 1: one more entry; kind 2: another layout) in the same
+    workspace: the plain moments of the states as they are, in the documented tree (tests/moment_tree_ref.py)."""
+    import moment_tree_ref as mt
+    got = e.pooled_moments()
+    np.testing.assert_array_equal(_bits(got), _bits(mt.pooled_moments_ref(e.theta(), np.asarray(pkw["par0"], float))), err_msg=msg)
+    assert got[0] == e.nchains, msg
+
+
+@pytest.mark.parametrize("name,extra,c0", [
+    ("scale_up", dict(doburnin=1, burnintime=260, badaptint=50, scalelimit=0.3), 1e-4),
+    ("greedy", dict(doburnin=1, burnintime=260, badaptint=50, scalelimit=0.15, greedy=1, initcmatn=7), 4e-3),
+])
+def test_pooled_burnin_rejection_count_over_two_tree_launches(oracle, name, extra, c0):
+    """The burn-in tick's vector (moments_kernel kind 1: the moments followed by the pooled rejection count) reduced over 66 tiles -- two launches
+    of the tile tree, a ragged last tile, a second group of two tiles -- against the tick-by-tick restatement; the rejection count steers the
+    factor (an `up` / `down` in the log), and the getter afterwards reduces the shorter plain vector in the same workspace."""
+    from mcmcf90_amd import engine_from_problem
+    d, N, nsimu = 3, 4163, 230
+    ckw = dict(nsimu=nsimu, adaptint=100, updatesigma=0, **extra)
+    S = 0.5 ** np.abs(np.subtract.outer(np.arange(d), np.arange(d)))
+    pkw = dict(kind="gauss", npar=d, par0=np.full(d, 0.3), cmat0=c0 * np.eye(d), mu=np.linspace(-1, 1, d), lam=np.linalg.inv(S))
+    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1)
+    e.init(); e.run()
+    chains, st, log = _restate_pooled(oracle, ckw, pkw, N)
+    msg = "%s; sampling kernel %s" % (log, e.last_kernel())
+    kinds = {k for _, k in log}
+    assert kinds & {"up", "down"}, msg                           # without one the kind-1 value steered nothing
+    if name == "greedy":
+        assert "greedy" in kinds, msg
+    theta = np.array([ch.theta for ch in chains])
+    np.testing.assert_array_equal(_bits(e.theta()), _bits(theta), err_msg=msg)
+    for c in (0, 4095, 4096, N - 1):
+        np.testing.assert_array_equal(e.accepted(c), chains[c].accepted, err_msg=msg)
+    cm, mean, W, R = e.pooled()
+    assert W == st["W"], msg
+    np.testing.assert_array_equal(_bits(np.triu(R)), _bits(np.triu(st["R"])), err_msg=msg)
+    np.testing.assert_array_equal(_bits(mean), _bits(np.array(st["mean"])), err_msg=msg)
+    _getter_after_tick(e, pkw, msg)
+    for ch in chains:
+        ch.close()
+    e.close()
+
+
 @pytest.mark.parametrize("name,extra,c0,kind", [
     ("dr_am", dict(drscale=2.0), 0.3, "gauss"),                                                          # second stage with the shared R2, iC
     ("dr_banana", dict(drscale=3.0), 1.0, "banana"),
@@ -937,6 +981,37 @@ def test_pooled_ram_matches_restatement(oracle, d, N, mfma, condmax, monkeypatch
     else:
         np.testing.assert_array_equal(_bits(np.triu(e.pooled()[3])), _bits(R))
     assert not np.array_equal(R, st["R"])                       # the factor did adapt
+    for ch in chains:
+        ch.close()
+    e.close()
+
+
+@pytest.mark.parametrize("condmax", [0.0, 1e8])
+def test_pooled_ram_statistic_over_two_tree_launches(oracle, condmax):
+    """The pooled RAM statistic (moments_kernel kind 2) reduced over 66 tiles -- two launches of the tile tree, a ragged last tile, a second group
+    of two tiles -- with the Cholesky and the SVD factor, against the tick-by-tick restatement; the getter afterwards reduces the plain
+    moments, a vector of another length, in the same workspace.  (The engine picks the sampling kernel: it is not the subject here.)"""
+    from mcmcf90_amd import engine_from_problem
+    d, N = 3, 4163
+    nsimu, adaptint, nu, target = 130, 20, 0.7, 0.234
+    ckw = dict(nsimu=nsimu, method="ram", adaptint=adaptint, updatesigma=0, nuparam=nu, alphatarget=target, condmax=condmax)
+    rng = np.random.default_rng(d)
+    A = rng.standard_normal((d, d)) / np.sqrt(d)
+    pkw = dict(kind="gauss", npar=d, par0=np.full(d, 0.2), cmat0=(0.5 / d) * np.eye(d), mu=np.zeros(d), lam=A @ A.T + np.eye(d))
+    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1)
+    e.init(); e.run()
+    msg = "condmax %g; sampling kernel %s" % (condmax, e.last_kernel())
+    chains, R, st, floored = _restate_pooled_ram(oracle, ckw, pkw, N)
+    theta = np.array([ch.theta for ch in chains])
+    np.testing.assert_array_equal(_bits(e.theta()), _bits(theta), err_msg=msg)
+    for c in (0, 4095, 4096, N - 1):
+        np.testing.assert_array_equal(e.accepted(c), chains[c].accepted, err_msg=msg)
+    if condmax > 0.0:
+        np.testing.assert_array_equal(_bits(e.pooled()[3]), _bits(R), err_msg=msg)
+    else:
+        np.testing.assert_array_equal(_bits(np.triu(e.pooled()[3])), _bits(R), err_msg=msg)
+    assert not np.array_equal(R, st["R"]), msg                  # the factor did adapt
+    _getter_after_tick(e, pkw, msg)
     for ch in chains:
         ch.close()
     e.close()
