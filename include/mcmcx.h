@@ -219,6 +219,37 @@ int32_t mcmcx_pooled_moments_len(mcmcx_handle h);
  * the engine's stream */
 int mcmcx_pooled_moments_dev(mcmcx_handle h, void *dev_out);
 
+/* ---- thinned samples of ALL chains, kept on the device (no counterpart in the single-chain reference, whose chain / sschain /
+ * s2chain arrays -- record_chain, mcmcx_get_chain -- hold every row of one chain).
+ * mcmcx_set_samples, before mcmcx_init: iteration i, 1 <= i <= nsimu, is kept when i >= first and (i - first) % thin == 0, in a ring
+ * of `capacity` slots (once it is full the oldest sample is overwritten); thin = 0 switches sampling off again (the default).
+ * Iteration 1 is the state mcmcx_init leaves (the reference's chain row 1; mcmcx_simuind is 1 after init), so first = 1 keeps the
+ * start point, stored at init.  Refused with -47: first < 1, thin < 0, capacity < 1 with thin > 0, a call after mcmcx_init, and
+ * mcmcx_set_target_external (the engine does not run the iterations there; mcmcx_init returns the -47 when the external target was
+ * chosen after this call).  The store -- capacity x ceil(nchains / 64) x 64 x nfields doubles -- is allocated by mcmcx_init with
+ * the engine's other device state; if that fails, init fails with the size in its message.
+ * How: a kept iteration ends the launch of the sampling kernel, like an adaptation tick does, and a copy kernel of its own stores
+ * the state the launch wrote back; no sampling kernel knows about the store.  Launch boundaries do not matter to the chains, so a
+ * run with sampling on is bit-identical -- states, stream positions, factors, counters -- to the same run without it, and
+ * mcmcx_kernel_time / mcmcx_last_kernel keep describing the sampling kernels alone.  The cost is the copy plus one more launch per
+ * kept iteration: the lane-group kernels reload their factors into registers at every launch, so a small thin costs them
+ * throughput ("Thinned samples", has the measured table). */
+int mcmcx_set_samples(mcmcx_handle h, int32_t first, int32_t thin, int32_t capacity);
+/* Returns the number of samples retained now (0 before any was kept or with sampling off): retained sample s (0 = oldest) is
+ * iteration oldest_iteration + s * thin.  nfields = npar + 2 nycol + 1: the fields of one chain are theta[npar], ss[nycol], sspri,
+ * sigma2[nycol].  Valid after a run that returned MCMCX_INTERRUPTED, for the iterations up to mcmcx_simuind.  The out arguments
+ * may be NULL.  (No counterpart in the reference.) */
+int32_t mcmcx_samples_kept(mcmcx_handle h, int32_t *oldest_iteration, int32_t *thin, int32_t *nfields);
+/* Retained samples s0 .. s0 + ns - 1 of chains c0 .. c0 + nc - 1 (no counterpart in the reference).  layout 0: [ns][nc][nfields],
+ * one chain's fields contiguous like mcmcx_get_theta's rows; layout 1: [ns][nfields][nc], the chain index running fastest.
+ * mcmcx_get_samples copies to host memory and synchronises; mcmcx_get_samples_dev writes into the caller's DEVICE buffer and is
+ * asynchronous on the engine's stream like mcmcx_pooled_moments_dev (mcmcx_sync before another stream reads it).  A window outside
+ * the retained samples or the chains, ns < 1, nc < 1 or another layout is refused with -48 before anything is launched.
+ * mcmcx_get_samples stages the WHOLE window in a temporary device buffer of ns x nc x nfields doubles, on top of the ring (the
+ * size is in the message if that allocation fails): at large chain counts read a few samples per call, or use the _dev form. */
+int mcmcx_get_samples(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_t nc, int32_t layout, double *host_out);
+int mcmcx_get_samples_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_t nc, int32_t layout, void *dev_out);
+
 /* Pooled mode across several GPUs: at every adaptation tick the engine writes its local moment vector
  * (mcmcx_pooled_moments_len doubles) to dev_buf, synchronises its stream and calls fn(user); fn must sum dev_buf
  * over all ranks in place (an RCCL all-reduce) and return after the result is visible.  Without a hook the local
@@ -266,6 +297,9 @@ int mcmcx_kernel_time(mcmcx_handle h, double *ms, int64_t *launches, int64_t *st
 int mcmcx_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out);
 int mcmcx_debug_rng(uint32_t seed, uint32_t chain_id, int32_t kind, int32_t n, double a, double b, double *out,
                     uint64_t *nused);
+/* element offset of row `field` of tile `tile` in slot `slot` of the sample store, [slot][ntiles][nfields][64] doubles: the host
+ * build of the one function the store's kernels index with (no reference counterpart; a test checks it beyond 2**32).  Needs no device. */
+int64_t mcmcx_debug_samples_offset(int64_t slot, int64_t ntiles, int64_t nfields, int64_t tile, int64_t field);
 /* The engine's kernel-selection tables (which sampling kernel a configuration runs: launch_step / launch_group / launch_scam of
  * mcx_api.hip), entry `index` as "family:name" into buf -- the name mcmcx_last_kernel reports after a run.  Returns the number
  * of entries (index = -1, buf = NULL: count only).  Needs no device.  tests/test_kernel_table.py requires a parity test per entry. */

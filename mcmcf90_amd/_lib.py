@@ -106,6 +106,12 @@ SYMBOLS["mcmcx_set_target_external"] = (C.c_int, [C.c_void_p])
 SYMBOLS["mcmcx_run1_decide"] = (C.c_int, [C.c_void_p, C.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP])
 SYMBOLS["mcmcx_run1_propose"] = (C.c_int, [C.c_void_p, C.c_int32, _DP, _DP])
 SYMBOLS["mcmcx_run1_sscrit"] = (C.c_int, [C.c_void_p, _DP, _DP, _DP])
+# thinned samples of all chains, kept on the device
+SYMBOLS["mcmcx_set_samples"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32])
+SYMBOLS["mcmcx_samples_kept"] = (C.c_int32, [C.c_void_p, _IP, _IP, _IP])
+SYMBOLS["mcmcx_get_samples"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP])
+SYMBOLS["mcmcx_get_samples_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p])
+SYMBOLS["mcmcx_debug_samples_offset"] = (C.c_int64, [C.c_int64] * 5)
 
 _lib = None
 

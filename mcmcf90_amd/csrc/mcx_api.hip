@@ -6,8 +6,8 @@
 // form.  No CPU fallback: every numerical step of the sampler runs in the HIP kernels
 // of mcx_kernels.hpp; without a GPU every entry point that needs one fails.
 // ONE translation unit: the host parts below are included in order (engine object, initial factor, kernel selection and
-// launchers, adaptation tick, pooled mode and communicator, host callbacks); this file holds the extern "C" entry points and
-// mcmcx_init's steps.
+// launchers, the sample store, adaptation tick, pooled mode and communicator, host callbacks); this file holds the extern "C" entry
+// points and mcmcx_init's steps.
 #include <hip/hip_runtime.h>
 #include <csignal>
 #include <cmath>
@@ -26,6 +26,7 @@
 #include "mcx_host_engine.hpp"
 #include "mcx_host_linalg.hpp"
 #include "mcx_host_launch.hpp"
+#include "mcx_host_samples.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
 #include "mcx_host_callbacks.hpp"
@@ -232,6 +233,19 @@ int mcmcx_set_target_external(mcmcx_handle h)
     return 0;
 }
 
+int mcmcx_set_samples(mcmcx_handle h, int32_t first, int32_t thin, int32_t capacity)
+{
+    if (!h) return fail(-1, "null handle");
+    if (h->inited) return fail(-47, "mcmcx_set_samples after mcmcx_init (the store is allocated there)");
+    if (thin > 0 && h->external) return fail(-47, "mcmcx_set_samples: not with mcmcx_set_target_external (the caller drives the "
+        "iterations)");
+    if (first < 1 || thin < 0 || (thin > 0 && capacity < 1)) return fail(-47, "mcmcx_set_samples: first >= 1, thin >= 0 and, with "
+        "thin > 0, capacity >= 1 (first = " + std::to_string(first) + ", thin = " + std::to_string(thin) + ", capacity = " +
+        std::to_string(capacity) + ")");
+    h->samp.first = first; h->samp.thin = thin; h->samp.capacity = thin > 0 ? capacity : 0;
+    return 0;
+}
+
 int mcmcx_set_target_module(mcmcx_handle h, const char *code_object_path, const char *kernel_name, const void *userdata, int64_t nbytes)
 {
     if (!h || !code_object_path || !kernel_name) return fail(-1, "mcmcx_set_target_module: null argument");
@@ -316,6 +330,8 @@ static int init_check(mcmcx_engine *h)
     if (h->tkind == TGT_EXPCOLS
         && h->tncols != ny) return fail(-36, "response-column target: mcmcx_set_sigma2nobs must give one sigma2 / nobs per column");
     if (h->tkind < 0) return fail(-31, "no target: the device engine needs mcmcx_set_target_*");
+    if (h->external && h->samp.thin > 0) return fail(-47, "mcmcx_set_samples: not with mcmcx_set_target_external (the caller drives the "
+        "iterations)");
     return 0;
 }
 static int initial_factor(mcmcx_engine *h, InitialFactor &f)
@@ -529,7 +545,8 @@ int mcmcx_init(mcmcx_handle h)
         if (h->dodr) pooled_dr_fresh(h);
         if ((rc = pooled_alloc(h)) || (rc = pooled_upload(h))) return rc;
     }
-    if ((rc = init_run_buffers(h)) || (rc = init_fill(h, f))) return rc;
+    if ((rc = init_run_buffers(h)) || (rc = samples_alloc(h)) || (rc = init_fill(h, f))) return rc;
+    if (sample_due(h, 1) && (rc = samples_keep(h, 1))) return rc;         // iteration 1 is the start point (the reference's chain row 1)
     h->simuind = 1;
     h->inited = true;
     return 0;
@@ -596,10 +613,10 @@ static int run_impl(mcmcx_handle h, int32_t upto)
         }
         int end = it, mode = 0;
         bool ramtick = false;
-        for (;; ++end) {                                    // extend the launch up to the next tick
+        for (;; ++end) {                                    // extend the launch up to the next tick or kept iteration
             mode = adapt_mode(c, end);
             ramtick = pooled_ram_due(h, end);
-            if (mode != 0 || ramtick || end == upto || end - it + 1 >= maxseg) break;
+            if (mode != 0 || ramtick || sample_due(h, end) || end == upto || end - it + 1 >= maxseg) break;
         }
         if (phase_cut(h)) {
             for (int i2 = it; i2 <= end; ++i2) { int rc = host_iteration(h, i2, i2 < end); if (rc) { h->failed = true; return rc; } }
@@ -635,6 +652,9 @@ static int run_impl(mcmcx_handle h, int32_t upto)
         }
         if (ramtick && trc == 0) trc = pooled_ram_tick(h, end);
         if (trc) return trc;
+        // a kept iteration (mcmcx_set_samples): the state the launch wrote back, behind the tick (which does not move theta) and outside
+        // the step kernels' event pair
+        if (sample_due(h, end)) { int rc = samples_keep(h, end); if (rc) return rc; }
         if (h->stop_seen) {                                 // every rank read the same summed stop flag at this tick: leave together,
             h->stop_seen = false;                           // after iteration `end` WITH its adaptation applied (a resumed run
             int rc = mcmcx_sync(h); if (rc) return rc;      // continues at end + 1 like an uninterrupted one)
@@ -942,6 +962,36 @@ int mcmcx_get_chain(mcmcx_handle h, int32_t chain, double *chain_out, double *ss
     return 0;
 }
 
+int32_t mcmcx_samples_kept(mcmcx_handle h, int32_t *oldest_iteration, int32_t *thin, int32_t *nfields)
+{
+    if (!h) return -1;
+    const long long have = samples_retained(h);
+    if (oldest_iteration) *oldest_iteration = (int32_t)(h->samp.first + (h->samp.kept - have) * h->samp.thin);
+    if (thin) *thin = h->samp.thin;
+    if (nfields) *nfields = samples_nfields(h);
+    return (int32_t)have;
+}
+
+int mcmcx_get_samples_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_t nc, int32_t layout, void *dev_out)
+{
+    int rc = samples_check(h, s0, ns, c0, nc, layout, dev_out, "mcmcx_get_samples_dev"); if (rc) return rc;
+    return samples_read(h, s0, ns, c0, nc, layout, (double *)dev_out);
+}
+
+int mcmcx_get_samples(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_t nc, int32_t layout, double *host_out)
+{
+    int rc = samples_check(h, s0, ns, c0, nc, layout, host_out, "mcmcx_get_samples"); if (rc) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t bytes = (size_t)ns * (size_t)nc * (size_t)samples_nfields(h) * sizeof(double);
+    DevBufs g;
+    double *tmp = nullptr;
+    if (g.alloc(&tmp, bytes) != hipSuccess) return fail(-101, "mcmcx_get_samples: hipMalloc of " + std::to_string(bytes) + " bytes failed");
+    if ((rc = samples_read(h, s0, ns, c0, nc, layout, tmp))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, tmp, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int32_t mcmcx_pooled_moments_len(mcmcx_handle h) { return h ? 1 + h->d + h->P : -1; }
 
 static int pooled_vec_len(const mcmcx_engine *h, int kind) { return kind == 2 ? 2 + h->P : 1 + h->d + h->P + (kind == 1 ? 1 : 0); }
@@ -1095,6 +1145,11 @@ int mcmcx_debug_kernel_table(int32_t index, char *buf, int32_t len)
         total += (int)ns[t];
     }
     return total;
+}
+
+int64_t mcmcx_debug_samples_offset(int64_t slot, int64_t ntiles, int64_t nfields, int64_t tile, int64_t field)
+{
+    return (int64_t)samples_row((size_t)slot, (size_t)ntiles, (size_t)nfields, (size_t)tile, (size_t)field);
 }
 
 int mcmcx_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out)

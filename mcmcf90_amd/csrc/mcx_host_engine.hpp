@@ -113,9 +113,13 @@ struct PooledState {
     double *d_R2T = nullptr, *d_iCd = nullptr;           // SH_DRT: R2 dense, iC dense and symmetric -- pooled_mfma_kernel<true>
     double *d_U = nullptr;                               // SH_U: [U col-major | pad | U row-major | pad | std] -- scam_pooled[12]_kernel
 };                                                       // (SH_UREP: U and std copied to every chain's E.Rf / E.qstd -- npar > 240)
+// The thinned sample store (mcmcx_set_samples): iteration i is kept when i >= first and (i - first) % thin == 0 (thin = 0: off), in slot
+// (number kept before it) % capacity of the ring `store`, [capacity][ntiles][nfields][64] doubles (mcx_samples.hpp)
+struct SamplePlan { int first = 1, thin = 0, capacity = 0; long long kept = 0; double *store = nullptr; };
 struct mcmcx_engine {
     mcmcx_config cfg;
     KernelPlan plan;
+    SamplePlan samp;
     int d = 0, P = 0, ntiles = 0, nlanes = 0;
     int dodr = 0, usesvd = 0;
     bool inited = false;

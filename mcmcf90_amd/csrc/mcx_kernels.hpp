@@ -20,6 +20,7 @@
 //   mcx_adapt.hpp     init_kernel, adapt_pre / adapt_cov_diag / adapt_cov_off / adapt_covb_* / adapt_post kernels
 //   mcx_svd.hpp       svd_sweep_stream(32)_kernel, svd_applyv_stream32_kernel, tile <-> chain layout conversion
 //   mcx_moments.hpp   moments_kernel, moments_tree_kernel, debug kernels
+//   mcx_samples.hpp   samples_keep_kernel, samples_read_rows_kernel / samples_read_chains_kernel (the thinned sample store)
 // The lane-GROUP kernels (16 / 4 lanes per chain, factors on chip) are mcx_group.hpp and mcx_group_ram.hpp.
 // Kernel forms that were measured and lost, or that a later form superseded, are not in the product library: tools/variants/README.md.
 #pragma once
@@ -34,3 +35,4 @@
 #include "mcx_adapt.hpp"
 #include "mcx_svd.hpp"
 #include "mcx_moments.hpp"
+#include "mcx_samples.hpp"

@@ -38,6 +38,28 @@ def make_config(npar, nchains=1, **kw):
     return c
 
 
+def sample_iterations(first, thin, capacity, simuind):
+    """The iterations a sample store retains once the run stands at `simuind` (mcmcx_set_samples' rule, stated once): iteration i,
+    1 <= i <= simuind, is kept when i >= first and (i - first) % thin == 0, and the ring holds the last `capacity` of those.
+    thin = 0 (sampling off) and first > simuind keep nothing."""
+    first, thin, capacity, simuind = int(first), int(thin), int(capacity), int(simuind)
+    if thin <= 0 or capacity < 1 or simuind < first:
+        return []
+    n = (simuind - first) // thin + 1
+    r = min(n, capacity)
+    return [first + (n - r + j) * thin for j in range(r)]
+
+
+def sample_nfields(npar, nycol=1):
+    """Doubles per chain and sample: theta[npar], ss[nycol], sspri, sigma2[nycol]."""
+    return int(npar) + 2 * int(nycol) + 1
+
+
+def sample_store_offset(slot, ntiles, nfields, tile, field):
+    """Element offset of a 64-chain row in the device store, [slot][ntiles][nfields][64] doubles (mcx_samples.hpp: samples_row)."""
+    return ((int(slot) * int(ntiles) + int(tile)) * int(nfields) + int(field)) * 64
+
+
 class Comm:
     """The node's communicator (include/mcmcx.h, "several GPUs of one node"): one process per GPU, RCCL underneath
     (backend "rccl"), or the host-staged transport for ranks that share one GPU (backend "host")."""
@@ -301,6 +323,49 @@ class Engine:
         ch = np.zeros((n, self.npar + 1)); ss = np.zeros((n, ny + 1)); s2 = np.zeros((n, ny)); nr = C.c_int32()
         self._chk(self.L.mcmcx_get_chain(self.h, chain, _dp(ch), _dp(ss), _dp(s2), C.byref(nr)))
         return ch[:nr.value], ss[:nr.value], (s2[:, 0] if ny == 1 else s2)
+
+    # --- thinned samples of all chains, kept on the device (mcmcx_set_samples)
+    def set_samples(self, first=1, thin=1, capacity=None):
+        """Keep iteration i when i >= first and (i - first) % thin == 0, in a ring of `capacity` samples (None: as many as the rule
+        keeps up to nsimu); thin = 0 switches sampling off.  Before init."""
+        if capacity is None:
+            capacity = max(1, len(sample_iterations(first, thin, self.nsimu + 1, self.nsimu))) if thin > 0 else 0
+        self._chk(self.L.mcmcx_set_samples(self.h, int(first), int(thin), int(capacity)))
+
+    def samples_kept(self):
+        """(n, oldest_iteration, thin, nfields): retained sample s (0 = oldest) is iteration oldest_iteration + s * thin."""
+        o, t, f = C.c_int32(), C.c_int32(), C.c_int32()
+        n = self.L.mcmcx_samples_kept(self.h, C.byref(o), C.byref(t), C.byref(f))
+        return int(n), o.value, t.value, f.value
+
+    def _sample_window(self, s0, ns, c0, nc, layout):
+        n, oldest, thin, nf = self.samples_kept()
+        ns = n - s0 if ns is None else int(ns)
+        nc = self.nchains - c0 if nc is None else int(nc)
+        its = np.array([oldest + (s0 + j) * thin for j in range(max(ns, 0))], dtype=np.int64)
+        shape = (ns, nc, nf) if layout == 0 else (ns, nf, nc)
+        return ns, nc, its, shape
+
+    def samples(self, s0=0, ns=None, c0=0, nc=None, layout=0):
+        """(iterations[ns], array): retained samples s0 .. s0 + ns - 1 of chains c0 .. c0 + nc - 1 as [ns][nc][nfields] (layout 0) or
+        [ns][nfields][nc] (layout 1); the fields of a chain are theta, ss per column, sspri, sigma2 per column."""
+        ns, nc, its, shape = self._sample_window(s0, ns, c0, nc, layout)
+        a = np.zeros(shape)
+        if ns == 0 or nc == 0:
+            return its, a
+        self._chk(self.L.mcmcx_get_samples(self.h, int(s0), ns, int(c0), nc, int(layout), _dp(a)))
+        return its, a
+
+    def samples_torch(self, s0=0, ns=None, c0=0, nc=None, layout=0):
+        """The same window as a float64 torch tensor on the engine's device: the copy never leaves device memory."""
+        import torch
+        ns, nc, its, shape = self._sample_window(s0, ns, c0, nc, layout)
+        t = torch.empty(shape, dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        if ns == 0 or nc == 0:
+            return its, t
+        self._chk(self.L.mcmcx_get_samples_dev(self.h, int(s0), ns, int(c0), nc, int(layout), C.c_void_p(t.data_ptr())))
+        self.sync()
+        return its, t
 
     def pooled_moments(self):
         n = self.L.mcmcx_pooled_moments_len(self.h)
