@@ -16,6 +16,7 @@ Each fixture holds: cfg_* (namelist values), problem arrays, and from the refere
     chaincmat, chainmean    mcmccovf.dat / mcmcmean.dat
     rng_n     number of uniforms the reference drew
     svd_s, svd_U, svd_ticks, rows_at_ticks   (c5 only) what MKL's dgesvd returned at MCMC_init and at each adaptation
+    thin_its, thin_rows   (tests/golden/long/ only) every 1000th iteration and the state the chain stood on there
 """
 import os
 import sys
@@ -136,10 +137,78 @@ def cases():
     from mcmcf90_amd.workloads import problem
     ckw, pkw, _ = problem("c5", 250, adaptint=100)
     c["c5_illcond200_scam"] = (ckw, pkw, 51)
+    # --- RAM at its target acceptance rate.  Every RAM fixture above starts from a narrow cmat0: the chain accepts most proposals and
+    # nearly every iteration is a Cholesky update (dchud).  Started at the target's own covariance the chain sits near alphatarget, and
+    # about three iterations in four are downdates (dchdd): config 4's target from its covariance 0.5**|i-j| ...
+    d = 50
+    c["c4t_gauss50_ram_target"] = (dict(nsimu=6000, method="ram", updatesigma=0),
+                                   dict(kind="gauss", npar=d, par0=np.zeros(d), cmat0=0.5 ** np.abs(np.subtract.outer(np.arange(d), np.arange(d))), mu=np.zeros(d),
+                                        lam=corr_gauss(d)), 7)
+    # ... and a dense target with non-default alphatarget / nuparam, bounds, priors on every second component and the sigma2 update
+    # (npar 24: two column panels of twelve on the device's wide kernel, the 32-column instantiation of its group kernel)
+    d = 24
+    A = np.random.default_rng(2411).standard_normal((d, d))
+    lam = A @ A.T / d + np.eye(d)
+    c["e11_gauss24_ram_target_opts"] = (dict(nsimu=4000, method="ram", updatesigma=1, alphatarget=0.4, nuparam=0.9),
+                                        dict(kind="gauss", npar=d, par0=np.full(d, 0.1), cmat0=np.linalg.inv(lam), mu=np.linspace(-0.5, 0.5, d),
+                                             lam=lam, sigma2=0.8, nobs=15, lo=np.full(d, -2.5), hi=np.full(d, 2.5),
+                                             pri_mu=np.zeros(d), pri_sig=np.where(np.arange(d) % 2 == 0, 2.0, 0.0)), 73)
     return c
 
 
 MKL_LOGGED = {"c5_illcond200_scam"}       # fixtures made with MKL's dgesvd + the call log instead of the pinned routine
+
+LONG_OUT = os.path.join(OUT, "long")      # kept out of golden_util.names(): the generic fixture tests record whole chains of 130 chains
+LONG_THIN = 1000
+
+
+def long_cases():
+    """name -> (cfg kwargs, Problem kwargs, chain_id) of the runs too long for the generic fixture tests (tests/golden/long/).
+    Besides what the other fixtures hold they store thin_its = LONG_THIN, 2 LONG_THIN, ... and thin_rows = the state the chain
+    stood on at those iterations, rebuilt from chain.mat's rows and run lengths; chaincmat / chainmean are left out (method = 'ram'
+    never updates them)."""
+    c = {}
+    d = 50      # BASELINE config 4 as written: nsimu = 200 000 from cmat0 = 0.01 I -- the start-up regime, then ~190 000 stationary iterations
+    c["c4_gauss50_ram_200k"] = (dict(nsimu=200000, method="ram", updatesigma=0),
+                                dict(kind="gauss", npar=d, par0=np.zeros(d), cmat0=0.01 * np.eye(d), mu=np.zeros(d),
+                                     lam=corr_gauss(d)), 7)
+    # (from that start the chain still accepts 86 % of its proposals after 200 000 iterations: 171 472 updates, 28 528 downdates.)
+    # The same length from the target's own covariance (fixture c4t_gauss50_ram_target's start): the chain sits at alphatarget
+    # throughout, ~150 000 downdates of one factor
+    c["c4t_gauss50_ram_target_200k"] = (dict(nsimu=200000, method="ram", updatesigma=0),
+                                        dict(kind="gauss", npar=d, par0=np.zeros(d), cmat0=0.5 ** np.abs(np.subtract.outer(np.arange(d), np.arange(d))),
+                                             mu=np.zeros(d), lam=corr_gauss(d)), 7)
+    return c
+
+
+def state_at(chain, its):
+    """Rows of chain.mat (theta..., repeat count) -> the state after iterations `its` (1 = the start point, MCMC_aux.F90:167-175).
+    tests/golden_util.py's state_at applies the same rule to the oracle's and the device's rows: keep the two alike."""
+    cum = np.cumsum(chain[:, -1].astype(np.int64))
+    return chain[np.searchsorted(cum, np.asarray(its, dtype=np.int64), side="left"), :-1]
+
+
+def main_long(only):
+    os.makedirs(LONG_OUT, exist_ok=True)
+    for name, (ckw, pkw, chain_id) in long_cases().items():
+        if only and name not in only:
+            continue
+        cfg = po.make_cfg(**ckw)
+        prob = po.Problem(**pkw)
+        r = rr.run_reference(cfg, prob, chain_id=chain_id, timeout=3000)
+        assert int(r.chain[:, -1].sum()) == cfg.nsimu
+        k = 16
+        its = np.arange(LONG_THIN, cfg.nsimu + 1, LONG_THIN, dtype=np.int32)
+        out = {"chain_id": chain_id, "rng_n": r.rng_n, "chainind": r.chainind, "runlen": r.chain[:, -1].astype(np.int32),
+               "rows_head": r.chain[:k, :-1], "rows_tail": r.chain[-k:, :-1], "ss_head": r.sschain[:k, 0], "ss_tail": r.sschain[-k:, 0],
+               "thin_its": its, "thin_rows": state_at(r.chain, its)}
+        for f, _ in po.Cfg._fields_:
+            out["cfg_" + f] = getattr(cfg, f)
+        for kk, v in pkw.items():
+            out["prob_" + kk] = np.asarray(v)
+        path = os.path.join(LONG_OUT, name + ".npz")
+        np.savez_compressed(path, **out)
+        print("%-28s chainind=%d rng_n=%d  %d bytes" % (name, r.chainind, r.rng_n, os.path.getsize(path)))
 
 
 def main():
@@ -180,6 +249,7 @@ def main():
             out["prob_" + kk] = np.asarray(v)
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
         print("%-28s chainind=%d rng_n=%d" % (name, r.chainind, r.rng_n))
+    main_long(only)
 
 
 if __name__ == "__main__":

@@ -337,11 +337,13 @@ def test_random_scam_configuration_npar_13_to_120(oracle, seed):
     _check_scam_npar(oracle, seed)
 
 
-def _check_larger_npar(oracle, seed, dlo=13, dhi=65):
-    from mcmcf90_amd import engine_from_problem
+def _draw_larger_npar(seed, dlo=13, dhi=65, method=None, target_start=None):
+    """The configuration _check_larger_npar runs.  method / target_start (tests/test_oracle_fuzz_reference.py's RAM seeds): the drawn
+    method and the drawn choice of cmat0 = inv(lam) replaced by the given ones; every other draw is taken as it comes."""
     r = np.random.default_rng(7000 + seed)
     d = int(r.integers(dlo, dhi))
-    method = str(r.choice(["ram", "ram", "dram", "er"]))
+    drawn = str(r.choice(["ram", "ram", "dram", "er"]))
+    method = drawn if method is None else method
     ckw = dict(nsimu=int(r.integers(50, 130)), method=method, adaptint=int(r.choice([15, 40])), updatesigma=int(r.random() < 0.3))
     if dlo > 64 and method == "dram" and d <= 130 and r.random() < 0.3:
         ckw.update(condmax=float(r.choice([1e6, 50.0])), adaptint=40)
@@ -354,8 +356,10 @@ def _check_larger_npar(oracle, seed, dlo=13, dhi=65):
     A = r.standard_normal((d, d)) / np.sqrt(d)
     lam = A @ A.T + np.eye(d)
     cmat0 = np.diag(r.uniform(0.2, 1.0, d)) / d
-    if method == "ram" and r.random() < 0.5:
-        cmat0 = np.linalg.inv(lam)                 # at the target acceptance rate: most iterations downdate
+    if method == "ram":
+        at_target = r.random() < 0.5
+        if at_target if target_start is None else target_start:
+            cmat0 = np.linalg.inv(lam)             # at the target acceptance rate: most iterations downdate
     pkw = dict(kind="gauss", npar=d, par0=r.standard_normal(d) * 0.1, cmat0=cmat0, mu=np.zeros(d), lam=lam)
     if ckw["updatesigma"]:
         pkw.update(sigma2=float(r.uniform(0.5, 1.5)), nobs=int(r.integers(5, 40)))
@@ -363,6 +367,13 @@ def _check_larger_npar(oracle, seed, dlo=13, dhi=65):
         pkw.update(lo=np.full(d, -2.5), hi=np.full(d, 2.5))
     if r.random() < 0.25:
         pkw.update(pri_mu=np.zeros(d), pri_sig=np.where(r.random(d) < 0.5, 0.0, 2.0))
+    return ckw, pkw
+
+
+def _check_larger_npar(oracle, seed, dlo=13, dhi=65):
+    from mcmcf90_amd import engine_from_problem
+    ckw, pkw = _draw_larger_npar(seed, dlo, dhi)
+    d, method = pkw["npar"], ckw["method"]
     cfg = oracle.make_cfg(**ckw); prob = oracle.Problem(**pkw)
     e = engine_from_problem(ckw, pkw, nchains=66, chain_id0=seed, record_accept=1)
     try:

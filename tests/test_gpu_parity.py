@@ -41,6 +41,7 @@ LANE_KERNEL = {
     "e8_nan_target_dr": "step_kernel_dr", "s1_gauss6_scam": "scam_mw_kernel<8>", "s2_gauss6_dram_svd": "step_kernel_ldsv",
     "s3_gauss6_dram_svd_dr": "step_kernel_dr", "s4_expdata_scam_s2": "scam_mw_kernel<8>", "s5_banana20_scam": "scam_mw_kernel<8>",
     "e9_gauss260_am": "step_kernel<false, false, false>", "e10_gauss260_ram": "step_kernel_ram_wide",       # npar above 256 (round 5), from the real reference
+    "c4t_gauss50_ram_target": "step_kernel_ram_wide", "e11_gauss24_ram_target_opts": "step_kernel_ram_wide",  # RAM at its target rate: mostly downdates
 }
 
 
@@ -109,6 +110,41 @@ def test_engine_matches_oracle_and_reference(oracle, name, kernels):
     o = oracle.run_chain(cfg, prob, chain_id=(cid - off) + 129)
     np.testing.assert_array_equal(_bits(th[129]), _bits(o.theta))
     assert _bits(sc[129, 0]) == _bits(np.float64(o.ss1)) and sc[129, 2] == o.sigma2       # (bits: fixture e8's ss is NaN)
+    e.close()
+
+
+@pytest.mark.parametrize("kernel,env", [("step_kernel<true, false, false>", dict(MCMCX_RAM_WIDE="0", MCMCX_RAM_GROUP="0")),
+                                        ("group_ram_kernel", dict(MCMCX_RAM_GROUP="1"))], ids=["narrow", "group"])
+def test_ram_forms_on_the_target_rate_fixture(oracle, kernel, env, monkeypatch):
+    """c4t_gauss50_ram_target -- config 4's target started at its own covariance, from the real reference: an accept rate of 0.225, three
+    iterations in four a Cholesky downdate (dchdd) over three or five column panels -- on the two RAM forms the generic fixture test does
+    not run: the panels of ten and the lane-group kernel.  70 chains, the fixture's stream on chain 1: its accept sequence and stream
+    position against the reference; state and factor of six chains (slots 0..3 of the first group wave, both sides of the tile
+    boundary's ragged end) against the oracle, bit for bit."""
+    from mcmcf90_amd import engine_from_problem
+    z, cfg, prob = load("c4t_gauss50_ram_target", oracle)
+    ckw, pkw = _kw(z)
+    cid, off = int(z["chain_id"]), 1
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    e = engine_from_problem(ckw, pkw, nchains=70, chain_id0=cid - off, record_accept=1)
+    e.init(); e.run()                                           # (all 6000 iterations: 2.7 s on the panels of ten, 0.6 s on the group kernel)
+    assert e.last_kernel() == kernel, e.last_kernel()
+    assert e.simuind == cfg.nsimu
+    np.testing.assert_array_equal(e.accepted(off), accepted_from_runlen(z["runlen"]))
+    th = e.theta()
+    assert e.rng(off)[0] == int(z["rng_n"])
+    scale = np.maximum(np.abs(z["rows_tail"]).max(axis=0), 1e-3)
+    assert np.max(np.abs(th[off] - z["rows_tail"][-1]) / scale) < 1e-7
+    assert e.totals()["downdates"] > 0.6 * 70 * cfg.nsimu          # the regime the fixture is about
+    for c in (0, off, 2, 3, 63, 69):
+        o = oracle.run_chain(cfg, prob, chain_id=cid - off + c, continue_on_downdate_fail=True)
+        np.testing.assert_array_equal(e.accepted(c), o.accepted)
+        np.testing.assert_array_equal(_bits(th[c]), _bits(o.theta))
+        np.testing.assert_array_equal(_bits(np.triu(e.R(c))), _bits(np.triu(o.R)))
+        cnt = e.counters(c)
+        assert e.rng(c)[0] == o.rng_n and (cnt["stayed"], cnt["bndstayed"]) == (o.stayed, o.bndstayed)
+        assert bool(cnt["status"] & 1) == (o.ram_downdate_fail != 0)
     e.close()
 
 

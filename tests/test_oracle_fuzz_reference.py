@@ -353,3 +353,30 @@ def test_oracle_equals_reference_ram_with_svd_factor(oracle, seed):
     assert np.max(np.abs(r.chain[:, :-1] - o.chain[:, :-1]) / scale) < 1e-7, ckw
     if cfg.updatesigma:
         np.testing.assert_allclose(r.s2chain, o.s2chain, rtol=1e-7)
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_oracle_equals_reference_ram_larger_npar(oracle, seed):
+    """method = 'ram' at npar 13..64 -- several column panels on the device -- for 300..600 iterations: the draw of
+    tests/test_gpu_fuzz.py's _check_larger_npar with its method fixed (alphatarget, nuparam, bounds, priors and the sigma2 update
+    as drawn), the even seeds from cmat0 = inv(lam), where the chain sits at its target rate and most iterations are
+    Cholesky downdates (dchdd), the odd ones from the drawn diagonal.  The fuzz seeds above stop at npar 12 and 260
+    iterations from a diagonal start; the device is compared with the oracle in this regime, so the oracle has to be the
+    reference there."""
+    from oracle import refrun as rr
+    if not rr.available():
+        pytest.skip("oracle/_ref/mcxref not built (needs /root/reference)")
+    ckw, pkw = _gen._draw_larger_npar(seed, method="ram", target_start=(seed % 2 == 0))
+    ckw["nsimu"] = 300 + (seed * 131) % 301
+    assert ckw["method"] == "ram" and 13 <= pkw["npar"] <= 64 and 300 <= ckw["nsimu"] <= 600
+    cfg = oracle.make_cfg(**ckw)
+    prob = oracle.Problem(**pkw)
+    o = oracle.run_chain(cfg, prob, chain_id=seed)
+    if o.ram_downdate_fail:                                   # the reference stops there: compared up to the stop, and the stop asserted
+        cfg, o = _prefix_before_failed_downdate(oracle, rr, ckw, cfg, prob, seed, o)
+        if cfg is None:
+            return
+    r = rr.run_reference(cfg, prob, chain_id=seed)
+    _agree(r, o, cfg, ckw)
+    if seed % 2 == 0:                                         # the regime the even seeds are about
+        assert (~o.accepted.astype(bool)).sum() > 0.4 * len(o.accepted), ckw

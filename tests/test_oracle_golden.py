@@ -4,7 +4,7 @@ chain.mat, MCMC_aux.F90:167-175) and the number of uniforms drawn must be identi
 floating-point chain agrees to the BLAS/libm rounding difference (reference = MKL + glibc)."""
 import numpy as np
 import pytest
-from golden_util import names, load, accepted_from_runlen
+from golden_util import names, load, accepted_from_runlen, state_at, LONG_RTOL
 
 RTOL = 1e-7      # relative to the column scale; observed <= 5e-9
 
@@ -34,6 +34,32 @@ def test_oracle_matches_reference_fixture(oracle, name):
     cs = max(np.max(np.abs(z["chaincmat"])), 1e-300)             # (a chain that never moves -- fixture e8 -- has covariance 0)
     assert np.max(np.abs(o.chaincmat - z["chaincmat"])) / cs < 1e-9
     np.testing.assert_allclose(o.chainmean, z["chainmean"], rtol=1e-9, atol=1e-9 * np.abs(z["chainmean"]).max() + 1e-12)
+
+
+@pytest.mark.parametrize("name,rows", [("c4_gauss50_ram_200k", 171472), ("c4t_gauss50_ram_target_200k", 47133)])
+def test_oracle_matches_the_200k_ram_fixtures(oracle, name, rows):
+    """method = 'ram', npar 50, nsimu = 200 000 from the real reference (tests/golden/long/): no other RAM fixture is longer than 6000
+    iterations, so neither the step-size table 1 / real(simuind)**nuparam beyond n = 6000 nor 200 000 accumulated dchud / dchdd sweeps
+    of one factor were ever compared.  BASELINE config 4 exactly as written (cmat0 = 0.01 I: the chain still accepts 86 % of its proposals
+    at the end -- 171 472 updates, 28 528 downdates), and the same run started at the target's own covariance (at alphatarget throughout:
+    152 867 downdates).  The whole run-length column, the stream position, the state at every 1000th iteration, the rows at both ends."""
+    z, cfg, prob = load("long/" + name, oracle)
+    assert int(z["chainind"]) == rows
+    assert cfg.nsimu == 200000 and cfg.method == 1 and list(z["thin_its"]) == list(range(1000, 200001, 1000))
+    o = oracle.run_chain(cfg, prob, chain_id=int(z["chain_id"]))
+    assert o.rc == 0 and not o.ram_downdate_fail
+    assert o.rng_n == int(z["rng_n"])
+    assert o.chainind == int(z["chainind"])
+    np.testing.assert_array_equal(o.chain[:, -1].astype(np.int32), z["runlen"])
+    np.testing.assert_array_equal(o.accepted, accepted_from_runlen(z["runlen"]))
+    k = z["rows_head"].shape[0]
+    scale = np.maximum(np.abs(z["rows_tail"]).max(axis=0), 1e-3)
+    dev = [np.max(np.abs(o.chain[:k, :-1] - z["rows_head"]) / scale), np.max(np.abs(o.chain[-k:, :-1] - z["rows_tail"]) / scale),
+           np.max(np.abs(state_at(o.chain[:, :-1], o.chain[:, -1], z["thin_its"]) - z["thin_rows"]) / scale)]
+    print("oracle against the reference, head / tail / thinned rows:", dev)
+    assert max(dev) < LONG_RTOL, dev
+    np.testing.assert_allclose(o.sschain[:k, 0], z["ss_head"], rtol=1e-7, atol=1e-9)
+    np.testing.assert_allclose(o.sschain[-k:, 0], z["ss_tail"], rtol=1e-7, atol=1e-9)
 
 
 def test_c5_fixture_through_two_adaptations_with_the_logged_factors(oracle):
