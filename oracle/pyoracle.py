@@ -207,6 +207,7 @@ def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_dow
         r.sigma2v = np.array(c.sigma2v[:ny]); r.ss1v = np.array(c.ss1v[:ny])
         r.theta = np.ctypeslib.as_array(c.oldpar, shape=(n,)).copy()
         r.ss1, r.sspri1 = c.ss1, c.sspri1
+        r.alpha12 = c.alpha12                      # the last first-stage alpha (MCMC_run_er never sets it)
         r.stayed, r.bndstayed, r.draccepted, r.drtries = c.stayed, c.bndstayed, c.draccepted, c.drtries
         r.nprop = c.nprop
         r.erstayed = c.erstayed
