@@ -250,6 +250,55 @@ int32_t mcmcx_samples_kept(mcmcx_handle h, int32_t *oldest_iteration, int32_t *t
 int mcmcx_get_samples(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_t nc, int32_t layout, double *host_out);
 int mcmcx_get_samples_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_t nc, int32_t layout, void *dev_out);
 
+/* ---- convergence summary of the retained samples, reduced on the device where the ring lies (no counterpart in the reference):
+ * posterior mean and standard deviation, split-R-hat, bulk ESS (Stan's multi-chain estimator over split chains with Geyer's initial
+ * monotone sequence) and MCSE of every field of the store.  Device scratch is ntiles x nfields x (maxlag + 3) doubles (plus nfields
+ * for the shift and one stats vector), not a copy of the window; no sampling kernel and no state of the run is touched, so a run
+ * with a summary call in the middle is the same run.  The definition is the contract -- sums in a fixed order, restated bit for bit
+ * in numpy by tests/diag_ref.py:
+ *   Window: retained samples s0 .. s0 + ns - 1 (ns >= 4) of ALL chains, oldest first.  n_h = ns / 2 (integer); half 0 is window
+ *   samples 0 .. n_h - 1, half 1 is ns - n_h .. ns - 1 (an odd ns drops the middle sample); K = min(maxlag, n_h - 1) with
+ *   0 <= maxlag <= MCMCX_DIAG_MAXLAG; M = 2 nchains split chains.
+ *   shift_f: the caller's shift[f], or with shift == NULL field f of chain 0 in window sample 0.
+ *   Per chain, half h and field f, in IEEE doubles without contraction:
+ *     y_i = x_i - shift_f;  s = (..((y_0 + y_1) + y_2) ..);  m = s / n_h;  z_i = y_i - m;
+ *     g_t = sum over i = 0 .. n_h - 1 - t, ascending, of z_i * z_{i+t} (a = a + z_i * z_{i+t} from +0.0), t = 0 .. K.
+ *   The chain's terms per field: m_0 + m_1, m_0 m_0 + m_1 m_1, g0_t + g1_t (t = 0 .. K).
+ *   Across chains, exactly the pooled moments' reduction: the 64 lanes of a tile in the adjacent-pairs tree, a lane without a chain
+ *   contributing +0.0, then the tiles in the fixed pairwise tree (for s = 1, 2, 4, ..: v[t] += v[t + s]; no partner, no addition).
+ *   Result per field: S1, S2, G_0 .. G_K.
+ *   The stats vector, 3 + nfields (maxlag + 4) doubles: [M, n_h, K, then per field: shift, S1, S2, G_0 .. G_maxlag], slots beyond K
+ *   +0.0.  It is additive over disjoint chain sets that used the same shift (add M and the sums): several ranks add their vectors
+ *   and finish; nothing collective happens here.
+ *   Finish (mcmcx_samples_diag: pure host, no handle, no device), per field, in this order:
+ *     W = G_0 / (M (n_h - 1));  Bn = (S2 - S1 S1 / M) / (M - 1);  varp = W (n_h - 1) / n_h + Bn;  rhat = sqrt(varp / W);
+ *     rho_0 = 1, rho_t = 1 - (W - G_t / (M n_h)) / varp;
+ *     pairs P_k = rho_2k + rho_2k+1 for k = 0 .. (K + 1) / 2 - 1: stop at the first P_k <= 0, each kept P_k := min(P_k, P_k-1);
+ *     tau = -1 + 2 sum of kept P_k;  tau = max(tau, 1 / log10(M n_h));  ess = M n_h / tau;
+ *     truncated = 1 if no pair stopped the sum, else 0;  mean = shift + S1 / M;  sd = sqrt(varp);  mcse = sd / sqrt(ess).
+ *   table[nfields][8]: mean, sd, rhat, ess, mcse, W, Bn, truncated.  truncated = 1: the lag window ended while the pairs were still
+ *   positive, so ess is an UPPER bound (raise maxlag, or thin more).  maxlag = 0 gives K = 0 and no pairs: ess and mcse are NaN
+ *   and truncated = 1 -- the R-hat-only mode.  Non-finite samples propagate.
+ * Reading the numbers: with n_h short against the autocorrelation time split-R-hat sits above 1 even at stationarity (an AR(1)
+ * with coefficient 0.5 and n_h = 32 gives 1.03, with 0.9 it gives 1.30): choose thin, not capacity, to fix it.  All chains start at
+ * par0, so R-hat here measures stationarity within the window, not recovery from dispersed starts.
+ * mcmcx_samples_stats copies the vector to host memory and synchronises; mcmcx_samples_stats_dev writes it into the caller's DEVICE
+ * buffer, asynchronous on the engine's stream.  shift, if given, is host memory in both forms; it is staged during the call, so it need
+ * only stay valid until the call returns.  Refused with -49 (the reason in
+ * mcmcx_last_error) before anything is launched: a null handle or output, an engine that is not inited, sampling off, ns < 4, a
+ * window outside the retained samples, maxlag outside 0 .. MCMCX_DIAG_MAXLAG.  The scratch is allocated at the first call, grows
+ * only and is freed by mcmcx_destroy; if the allocation fails the size is in the message (-101). */
+#define MCMCX_DIAG_MAXLAG 32
+/* 3 + nfields (maxlag + 4) (no counterpart in the reference) */
+int32_t mcmcx_samples_stats_len(mcmcx_handle h, int32_t maxlag);
+/* the stats vector of the window to host memory (no counterpart in the reference) */
+int mcmcx_samples_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift /* [nfields] host, or NULL */,
+                        double *host_out);
+/* ... into a device buffer, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, void *dev_out);
+/* the finish: stats vector (one engine's, or the sum of several) -> table[nfields][8] (no counterpart in the reference) */
+int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, double *table);
+
 /* Pooled mode across several GPUs: at every adaptation tick the engine writes its local moment vector
  * (mcmcx_pooled_moments_len doubles) to dev_buf, synchronises its stream and calls fn(user); fn must sum dev_buf
  * over all ranks in place (an RCCL all-reduce) and return after the result is visible.  Without a hook the local

@@ -112,6 +112,11 @@ SYMBOLS["mcmcx_samples_kept"] = (C.c_int32, [C.c_void_p, _IP, _IP, _IP])
 SYMBOLS["mcmcx_get_samples"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP])
 SYMBOLS["mcmcx_get_samples_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p])
 SYMBOLS["mcmcx_debug_samples_offset"] = (C.c_int64, [C.c_int64] * 5)
+# the store's convergence summary, reduced on the device; mcmcx_samples_diag is pure host
+SYMBOLS["mcmcx_samples_stats_len"] = (C.c_int32, [C.c_void_p, C.c_int32])
+SYMBOLS["mcmcx_samples_stats"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _DP])
+SYMBOLS["mcmcx_samples_stats_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_void_p])
+SYMBOLS["mcmcx_samples_diag"] = (C.c_int, [_DP, C.c_int32, C.c_int32, _DP])
 
 _lib = None
 

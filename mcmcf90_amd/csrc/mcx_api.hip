@@ -27,6 +27,7 @@
 #include "mcx_host_linalg.hpp"
 #include "mcx_host_launch.hpp"
 #include "mcx_host_samples.hpp"
+#include "mcx_host_diag.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
 #include "mcx_host_callbacks.hpp"
@@ -139,6 +140,7 @@ int mcmcx_destroy(mcmcx_handle h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto &p : h->pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (void *p : h->allocs) (void)hipFree(p);
+    if (h->d_diag) (void)hipFree(h->d_diag);                    // the summary's scratch (mcmcx_samples_stats)
     for (void *p : h->hallocs) (void)hipHostFree(p);
     h->h_cand.release(); h->h_ev.release(); h->h_hx.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -990,6 +992,40 @@ int mcmcx_get_samples(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(host_out, tmp, bytes, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ------------------------------------------------------------------ the sample store's convergence summary (mcx_host_diag.hpp)
+int32_t mcmcx_samples_stats_len(mcmcx_handle h, int32_t maxlag)
+{
+    if (!h) return fail(-49, "mcmcx_samples_stats_len: null handle");
+    if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-49, "mcmcx_samples_stats_len: maxlag " + std::to_string(maxlag) +
+        " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
+    return diag_stats_len(samples_nfields(h), maxlag);
+}
+
+int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, void *dev_out)
+{
+    int rc = diag_check(h, s0, ns, maxlag, dev_out, "mcmcx_samples_stats_dev"); if (rc) return rc;
+    return diag_launch(h, s0, ns, maxlag, shift, (double *)dev_out, nullptr);
+}
+
+int mcmcx_samples_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, double *host_out)
+{
+    int rc = diag_check(h, s0, ns, maxlag, host_out, "mcmcx_samples_stats"); if (rc) return rc;
+    double *staged = nullptr;
+    if ((rc = diag_launch(h, s0, ns, maxlag, shift, nullptr, &staged))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, double *table)
+{
+    if (!stats || !table) return fail(-49, "mcmcx_samples_diag: null argument");
+    if (nfields < 1) return fail(-49, "mcmcx_samples_diag: nfields < 1");
+    if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-49, "mcmcx_samples_diag: maxlag " + std::to_string(maxlag) +
+        " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
+    return diag_finish(stats, nfields, maxlag, table);
 }
 
 int32_t mcmcx_pooled_moments_len(mcmcx_handle h) { return h ? 1 + h->d + h->P : -1; }

@@ -176,6 +176,7 @@ struct mcmcx_engine {
     EngineDev E{};
     std::vector<void *> allocs;
     double *d_ramscale = nullptr, *d_moments = nullptr;
+    double *d_diag = nullptr; size_t diag_cap = 0;    // scratch of the sample store's summary (mcx_host_diag.hpp): first call, grows only
     // blocked SVD of the adaptation (large npar)
     double *d_Gc = nullptr, *d_Vc = nullptr, *d_svc = nullptr; uint8_t *d_need = nullptr, *d_state = nullptr; int *d_anyrot = nullptr;
     int wcap = 0;

@@ -60,6 +60,36 @@ def sample_store_offset(slot, ntiles, nfields, tile, field):
     return ((int(slot) * int(ntiles) + int(tile)) * int(nfields) + int(field)) * 64
 
 
+DIAG_MAXLAG = 32
+DIAG_COLUMNS = ("mean", "sd", "rhat", "ess", "mcse", "W", "Bn", "truncated")
+
+
+def samples_stats_len(nfields, maxlag):
+    """Doubles of a stats vector: [M, n_h, K, then per field: shift, S1, S2, G_0 .. G_maxlag] (mcmcx_samples_stats, include/mcmcx.h)."""
+    return 3 + int(nfields) * (int(maxlag) + 4)
+
+
+def samples_diag(stats, nfields, maxlag):
+    """[nfields][8] -- mean, sd, rhat, ess, mcse, W, Bn, truncated -- from a stats vector (one engine's, or the sum of several engines'
+    that used the same shift): mcmcx_samples_diag, pure host arithmetic, no engine and no device."""
+    L = _lib.load()
+    st = _f64(stats)
+    if st.size != samples_stats_len(nfields, maxlag):
+        raise McmcError("samples_diag: %d doubles given, nfields %d and maxlag %d make %d" % (st.size, nfields, maxlag,
+                                                                                            samples_stats_len(nfields, maxlag)))
+    table = np.zeros((int(nfields), 8))
+    if L.mcmcx_samples_diag(_dp(st), int(nfields), int(maxlag), _dp(table)) < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return table
+
+
+def sample_field_names(npar, nycol=1):
+    """Names of a sample's fields, in the store's order."""
+    ny = int(nycol)
+    return (["theta[%d]" % i for i in range(int(npar))] + (["ss"] if ny == 1 else ["ss[%d]" % j for j in range(ny)]) + ["sspri"]
+            + (["sigma2"] if ny == 1 else ["sigma2[%d]" % j for j in range(ny)]))
+
+
 class Comm:
     """The node's communicator (include/mcmcx.h, "several GPUs of one node"): one process per GPU, RCCL underneath
     (backend "rccl"), or the host-staged transport for ranks that share one GPU (backend "host")."""
@@ -366,6 +396,47 @@ class Engine:
         self._chk(self.L.mcmcx_get_samples_dev(self.h, int(s0), ns, int(c0), nc, int(layout), C.c_void_p(t.data_ptr())))
         self.sync()
         return its, t
+
+    # --- convergence summary of the retained samples, reduced on the device (mcmcx_samples_stats)
+    def _stats_window(self, s0, ns, shift):
+        """(ns, shift as a contiguous array or None) of a summary call; ns = None: every retained sample from s0 on."""
+        n, _, _, nf = self.samples_kept()
+        ns = n - s0 if ns is None else int(ns)
+        sh = None
+        if shift is not None:
+            sh = _f64(shift)
+            if sh.size != nf:
+                raise McmcError("samples_stats: shift has %d values, a sample has %d fields" % (sh.size, nf))
+        return ns, sh
+
+    def samples_stats(self, s0=0, ns=None, maxlag=16, shift=None):
+        """The stats vector of retained samples s0 .. s0 + ns - 1 of all chains (include/mcmcx.h has the definition): additive over engines
+        that were given the same `shift`; `samples_diag` finishes it."""
+        ns, sh = self._stats_window(s0, ns, shift)
+        a = np.zeros(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))))
+        self._chk(self.L.mcmcx_samples_stats(self.h, int(s0), ns, int(maxlag), _dp(sh), _dp(a)))
+        return a
+
+    def samples_stats_torch(self, s0=0, ns=None, maxlag=16, shift=None):
+        """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        import torch
+        ns, sh = self._stats_window(s0, ns, shift)
+        t = torch.empty(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))), dtype=torch.float64,
+                        device="cuda:%d" % self.cfg.device)
+        self._chk(self.L.mcmcx_samples_stats_dev(self.h, int(s0), ns, int(maxlag), _dp(sh), C.c_void_p(t.data_ptr())))
+        self.sync()
+        return t
+
+    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None):
+        """dict of arrays over the fields: mean, sd, rhat, ess, mcse, W, Bn, truncated; `fields` names the rows, `iterations` are the
+        window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound."""
+        _, oldest, thin, nf = self.samples_kept()
+        ns, sh = self._stats_window(s0, ns, shift)
+        table = samples_diag(self.samples_stats(s0, ns, maxlag, sh), nf, maxlag)
+        out = {k: table[:, j].copy() for j, k in enumerate(DIAG_COLUMNS)}
+        out["fields"] = sample_field_names(self.npar, getattr(self, "nycol", 1))
+        out["iterations"] = oldest + (int(s0) + np.arange(max(ns, 0), dtype=np.int64)) * thin
+        return out
 
     def pooled_moments(self):
         n = self.L.mcmcx_pooled_moments_len(self.h)
