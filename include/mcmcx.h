@@ -299,6 +299,50 @@ int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxl
 /* the finish: stats vector (one engine's, or the sum of several) -> table[nfields][8] (no counterpart in the reference) */
 int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, double *table);
 
+/* ---- exact order statistics, tail counts and quantiles of the retained samples, reduced on the device where the ring lies (no
+ * counterpart in the reference): credible intervals, medians and tail probabilities of every field without moving the window.  The
+ * r-th smallest of a multiset and an integer count depend on no order of summation, so the results are exact; the definition is
+ * restated in numpy by tests/quant_ref.py:
+ *   Window: retained samples s0 .. s0 + ns - 1 (ns >= 1) of ALL nchains chains; n = ns * nchains values per field, as int64_t (it
+ *   passes 2**31 at real sizes).  The padding lanes of the last tile are never counted.
+ *   Key: with b the double's bits, key(x) = b ^ (b >> 63 ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000).  The unsigned order of the keys
+ *   is the total order: negative NaNs < -inf < ... < -0.0 < +0.0 < ... < +inf < positive NaNs.  It is the key order, not the IEEE
+ *   comparison: -0.0 lies below +0.0 and NaNs take part.  On doubles that are no NaN it sorts as IEEE does.
+ *   Order statistic: os_f(r), 0 <= r < n, is the value of field f whose key is the r-th smallest of the window's n keys, returned
+ *   with its own bits (the inverse key map).
+ *   Counts: for a threshold x, lt_f(x) is the number of window values of field f with key < key(x), le_f(x) with key <= key(x).
+ *   Counts are additive over disjoint chain sets: several ranks bisect on summed counts for a rank of the union, and
+ *   le_f(x) / n is P(field f <= x); nothing collective happens here.
+ *   Quantile (Hyndman-Fan type 7, numpy's default position), in IEEE doubles without contraction:
+ *     pos = p * (double)(n - 1);  lo = floor(pos);  hi = min(lo + 1, n - 1);  g = pos - lo;  a = os(lo);  b = os(hi);
+ *     q = a when a and b have equal bits, otherwise q = a + (b - a) * g.
+ * How: a most-significant-digit radix select on the keys, eight passes of one byte, each streaming the window once and counting
+ * the digits of the values that match a rank's prefix with 64-bit integer atomics; no float atomic, no host round trip between the
+ * passes.  The counts are one pass.  No sampling kernel and no state of the run is touched: a run with these calls in the middle
+ * is the same run.  1 <= nr, nq <= MCMCX_QUANT_MAXR; ranks need be neither sorted nor distinct.  ranks, x and probs are host memory
+ * in every form and are staged during the call, so they need only stay valid until it returns.  The host forms copy the result and
+ * synchronise; the _dev forms write into the caller's DEVICE buffer, asynchronous on the engine's stream.  Device scratch is
+ * nfields x nr x 260 64-bit words, allocated at the first call, growing only, freed by mcmcx_destroy; if the allocation fails the
+ * size is in the message (-101).  Refused with -50 (the reason in mcmcx_last_error) on the host, before anything is launched or
+ * allocated: a null handle, output or argument array, an engine that is not inited, sampling off, ns < 1, a window outside the
+ * retained samples, nr or nq out of range, a rank outside 0 .. n - 1, a probability outside [0, 1] or NaN. */
+#define MCMCX_QUANT_MAXR 32
+/* os_f(ranks[k]) of every field to host memory, host_out[nfields][nr] (no counterpart in the reference) */
+int mcmcx_samples_order_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr, const int64_t *ranks /* [nr] host */,
+                              double *host_out);
+/* ... into a device buffer of nfields x nr doubles, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_order_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr, const int64_t *ranks, void *dev_out);
+/* lt and le of nq thresholds per field, x[nfields][nq] host -> host_out[nfields][nq][2] (no counterpart in the reference) */
+int mcmcx_samples_counts(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, int64_t *host_out);
+/* ... into a device buffer of nfields x nq x 2 64-bit integers, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_counts_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, void *dev_out);
+/* the quantile's positions: ranks[2 nq] = lo, hi per probability, frac[nq] = g.  Pure host, no handle, no device; refuses (-50) a p
+ * outside [0, 1], a NaN p and n < 1 (no counterpart in the reference) */
+int mcmcx_samples_quantile_ranks(int64_t n, int32_t nq, const double *probs, int64_t *ranks, double *frac);
+/* quantiles of every field, host_out[nfields][nq], nq <= MCMCX_QUANT_MAXR / 2: the ranks, their order statistics, the finish
+ * (no counterpart in the reference) */
+int mcmcx_samples_quantiles(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *probs, double *host_out);
+
 /* Pooled mode across several GPUs: at every adaptation tick the engine writes its local moment vector
  * (mcmcx_pooled_moments_len doubles) to dev_buf, synchronises its stream and calls fn(user); fn must sum dev_buf
  * over all ranks in place (an RCCL all-reduce) and return after the result is visible.  Without a hook the local
@@ -349,6 +393,13 @@ int mcmcx_debug_rng(uint32_t seed, uint32_t chain_id, int32_t kind, int32_t n, d
 /* element offset of row `field` of tile `tile` in slot `slot` of the sample store, [slot][ntiles][nfields][64] doubles: the host
  * build of the one function the store's kernels index with (no reference counterpart; a test checks it beyond 2**32).  Needs no device. */
 int64_t mcmcx_debug_samples_offset(int64_t slot, int64_t ntiles, int64_t nfields, int64_t tile, int64_t field);
+/* The order statistics' own kernels on a caller's array (no counterpart in the reference; tests only): values[n] is treated as a
+ * store of one slot, one field and ceil(n / 64) tiles with n chains, out[nr] takes os(ranks[k]).  A run cannot put +-0, +-inf,
+ * NaNs, denormals or values that differ in their last byte only into the ring; this can.  Refusals are -50. */
+int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int32_t nr, const int64_t *ranks, double *out);
+/* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
+ * inverse != 0 the bits whose key x's bits are.  Needs no device. */
+int64_t mcmcx_debug_quant_key(double x, int32_t inverse);
 /* The engine's kernel-selection tables (which sampling kernel a configuration runs: launch_step / launch_group / launch_scam of
  * mcx_api.hip), entry `index` as "family:name" into buf -- the name mcmcx_last_kernel reports after a run.  Returns the number
  * of entries (index = -1, buf = NULL: count only).  Needs no device.  tests/test_kernel_table.py requires a parity test per entry. */

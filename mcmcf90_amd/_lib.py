@@ -117,6 +117,16 @@ SYMBOLS["mcmcx_samples_stats_len"] = (C.c_int32, [C.c_void_p, C.c_int32])
 SYMBOLS["mcmcx_samples_stats"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _DP])
 SYMBOLS["mcmcx_samples_stats_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_void_p])
 SYMBOLS["mcmcx_samples_diag"] = (C.c_int, [_DP, C.c_int32, C.c_int32, _DP])
+# exact order statistics, tail counts and quantiles of the store; mcmcx_samples_quantile_ranks and mcmcx_debug_quant_key are pure host
+_LP = C.POINTER(C.c_int64)
+SYMBOLS["mcmcx_samples_order_stats"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _LP, _DP])
+SYMBOLS["mcmcx_samples_order_stats_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _LP, C.c_void_p])
+SYMBOLS["mcmcx_samples_counts"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _LP])
+SYMBOLS["mcmcx_samples_counts_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_void_p])
+SYMBOLS["mcmcx_samples_quantile_ranks"] = (C.c_int, [C.c_int64, C.c_int32, _DP, _LP, _DP])
+SYMBOLS["mcmcx_samples_quantiles"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _DP])
+SYMBOLS["mcmcx_debug_order_stats"] = (C.c_int, [C.c_int32, C.c_int64, _DP, C.c_int32, _LP, _DP])
+SYMBOLS["mcmcx_debug_quant_key"] = (C.c_int64, [C.c_double, C.c_int32])
 
 _lib = None
 

@@ -28,6 +28,7 @@
 #include "mcx_host_launch.hpp"
 #include "mcx_host_samples.hpp"
 #include "mcx_host_diag.hpp"
+#include "mcx_host_quant.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
 #include "mcx_host_callbacks.hpp"
@@ -141,6 +142,7 @@ int mcmcx_destroy(mcmcx_handle h)
     for (auto &p : h->pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (void *p : h->allocs) (void)hipFree(p);
     if (h->d_diag) (void)hipFree(h->d_diag);                    // the summary's scratch (mcmcx_samples_stats)
+    if (h->d_quant) (void)hipFree(h->d_quant);                  // the order statistics' scratch (mcmcx_samples_order_stats)
     for (void *p : h->hallocs) (void)hipHostFree(p);
     h->h_cand.release(); h->h_ev.release(); h->h_hx.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1028,6 +1030,64 @@ int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, dou
     return diag_finish(stats, nfields, maxlag, table);
 }
 
+// ------------------------------------------------------------------ order statistics, counts, quantiles of the store (mcx_host_quant.hpp)
+int mcmcx_samples_order_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr, const int64_t *ranks, void *dev_out)
+{
+    int rc = quant_check(h, s0, ns, nr, ranks, dev_out, "mcmcx_samples_order_stats_dev"); if (rc) return rc;
+    if ((rc = quant_check_ranks((long long)ns * h->cfg.nchains, nr, ranks, "mcmcx_samples_order_stats_dev"))) return rc;
+    return quant_order_stats(h, s0, ns, nr, ranks, (double *)dev_out, nullptr);
+}
+
+int mcmcx_samples_order_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr, const int64_t *ranks, double *host_out)
+{
+    int rc = quant_check(h, s0, ns, nr, ranks, host_out, "mcmcx_samples_order_stats"); if (rc) return rc;
+    if ((rc = quant_check_ranks((long long)ns * h->cfg.nchains, nr, ranks, "mcmcx_samples_order_stats"))) return rc;
+    double *staged = nullptr;
+    if ((rc = quant_order_stats(h, s0, ns, nr, ranks, nullptr, &staged))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, staged, (size_t)samples_nfields(h) * (size_t)nr * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mcmcx_samples_counts_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, void *dev_out)
+{
+    int rc = quant_check(h, s0, ns, nq, x, dev_out, "mcmcx_samples_counts_dev"); if (rc) return rc;
+    return quant_counts(h, s0, ns, nq, x, (unsigned long long *)dev_out, nullptr);
+}
+
+int mcmcx_samples_counts(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, int64_t *host_out)
+{
+    int rc = quant_check(h, s0, ns, nq, x, host_out, "mcmcx_samples_counts"); if (rc) return rc;
+    unsigned long long *staged = nullptr;
+    if ((rc = quant_counts(h, s0, ns, nq, x, nullptr, &staged))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, staged, (size_t)samples_nfields(h) * (size_t)nq * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mcmcx_samples_quantile_ranks(int64_t n, int32_t nq, const double *probs, int64_t *ranks, double *frac)
+{
+    if (!probs || !ranks || !frac) return fail(-50, "mcmcx_samples_quantile_ranks: null argument");
+    if (nq < 1) return fail(-50, "mcmcx_samples_quantile_ranks: nq < 1");
+    if (n < 1) return fail(-50, "mcmcx_samples_quantile_ranks: n < 1");
+    return quant_ranks((long long)n, nq, probs, ranks, frac);
+}
+
+int mcmcx_samples_quantiles(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *probs, double *host_out)
+{
+    int rc = quant_check(h, s0, ns, nq, probs, host_out, "mcmcx_samples_quantiles"); if (rc) return rc;
+    if (nq > MCMCX_QUANT_MAXR / 2) return fail(-50, "mcmcx_samples_quantiles: " + std::to_string(nq) + " probabilities, at most " +
+        std::to_string(MCMCX_QUANT_MAXR / 2) + " (two ranks each)");
+    int64_t ranks[MCMCX_QUANT_MAXR];
+    double frac[MCMCX_QUANT_MAXR / 2];
+    if ((rc = quant_ranks((long long)ns * h->cfg.nchains, nq, probs, ranks, frac))) return rc;
+    const int nf = samples_nfields(h);
+    std::vector<double> os((size_t)nf * (size_t)nq * 2);
+    if ((rc = mcmcx_samples_order_stats(h, s0, ns, 2 * nq, ranks, os.data()))) return rc;
+    quant_finish(os.data(), frac, nf, nq, host_out);
+    return 0;
+}
+
 int32_t mcmcx_pooled_moments_len(mcmcx_handle h) { return h ? 1 + h->d + h->P : -1; }
 
 static int pooled_vec_len(const mcmcx_engine *h, int kind) { return kind == 2 ? 2 + h->P : 1 + h->d + h->P + (kind == 1 ? 1 : 0); }
@@ -1186,6 +1246,36 @@ int mcmcx_debug_kernel_table(int32_t index, char *buf, int32_t len)
 int64_t mcmcx_debug_samples_offset(int64_t slot, int64_t ntiles, int64_t nfields, int64_t tile, int64_t field)
 {
     return (int64_t)samples_row((size_t)slot, (size_t)ntiles, (size_t)nfields, (size_t)tile, (size_t)field);
+}
+
+int64_t mcmcx_debug_quant_key(double x, int32_t inverse)
+{
+    unsigned long long b;
+    memcpy(&b, &x, 8);
+    return (int64_t)(inverse ? quant_unkey(b) : quant_key(b));
+}
+
+// the select's own kernels on a caller's array: a store of one slot, one field, ceil(n / 64) tiles and n chains; the padding lanes of
+// the last tile are filled with all-ones words (the smallest key there is), which a select that counted them would return
+int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int32_t nr, const int64_t *ranks, double *out)
+{
+    if (!values || !ranks || !out) return fail(-50, "mcmcx_debug_order_stats: null argument");
+    if (nr < 1 || nr > MCMCX_QUANT_MAXR) return fail(-50, "mcmcx_debug_order_stats: nr outside 1 .. " + std::to_string(MCMCX_QUANT_MAXR));
+    if (n < 1 || n > 2147483584ll) return fail(-50, "mcmcx_debug_order_stats: n outside 1 .. 2**31 - 64");
+    int rc = quant_check_ranks((long long)n, nr, ranks, "mcmcx_debug_order_stats"); if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const int T = (int)((n + 63) / 64);
+    DevBufs g;
+    double *store = nullptr, *dout = nullptr; unsigned long long *w = nullptr;
+    HIPCHK(g.alloc(&store, (size_t)T * 512)); HIPCHK(g.alloc(&dout, (size_t)nr * 8));
+    HIPCHK(g.alloc(&w, quant_select_words(1, nr) * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(store, 0xFF, (size_t)T * 512));
+    HIPCHK(hipMemcpy(store, values, (size_t)n * 8, hipMemcpyHostToDevice));
+    if ((rc = quant_select_launch(quant_window(store, 0, 1, T, 1, (int)n, 1), w, nr, ranks, dout, 0))) return rc;
+    HIPCHK(hipMemcpy(out, dout, (size_t)nr * 8, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int mcmcx_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out)

@@ -83,6 +83,28 @@ def samples_diag(stats, nfields, maxlag):
     return table
 
 
+QUANT_MAXR = 32
+
+
+def _lp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _i64(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+
+
+def samples_quantile_ranks(n, probs):
+    """(ranks[nq][2], frac[nq]) of the quantiles at `probs` among n values (Hyndman-Fan type 7: pos = p (n - 1), lo = floor(pos),
+    hi = min(lo + 1, n - 1), g = pos - lo): mcmcx_samples_quantile_ranks, pure host arithmetic, no engine and no device."""
+    L = _lib.load()
+    p = _f64(probs).ravel()
+    ranks, frac = np.zeros((p.size, 2), dtype=np.int64), np.zeros(p.size)
+    if L.mcmcx_samples_quantile_ranks(int(n), int(p.size), _dp(p), _lp(ranks), _dp(frac)) < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return ranks, frac
+
+
 def sample_field_names(npar, nycol=1):
     """Names of a sample's fields, in the store's order."""
     ny = int(nycol)
@@ -427,15 +449,63 @@ class Engine:
         self.sync()
         return t
 
-    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None):
+    # --- exact order statistics, tail counts and quantiles of the retained samples (mcmcx_samples_order_stats)
+    def _quant_window(self, s0, ns):
+        n, _, _, nf = self.samples_kept()
+        return (n - s0 if ns is None else int(ns)), nf
+
+    def samples_order_stats(self, ranks, s0=0, ns=None):
+        """[nfields][nr]: the values whose keys are the ranks[k]-th smallest (0-based) among the ns x nchains values of each field in
+        retained samples s0 .. s0 + ns - 1 (include/mcmcx.h has the key order: -0.0 below +0.0, NaNs at the two ends)."""
+        ns, nf = self._quant_window(s0, ns)
+        r = _i64(ranks).ravel()
+        a = np.zeros((nf, r.size))
+        self._chk(self.L.mcmcx_samples_order_stats(self.h, int(s0), ns, int(r.size), _lp(r), _dp(a)))
+        return a
+
+    def samples_order_stats_torch(self, ranks, s0=0, ns=None):
+        """The same as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        import torch
+        ns, nf = self._quant_window(s0, ns)
+        r = _i64(ranks).ravel()
+        t = torch.empty((nf, r.size), dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        self._chk(self.L.mcmcx_samples_order_stats_dev(self.h, int(s0), ns, int(r.size), _lp(r), C.c_void_p(t.data_ptr())))
+        self.sync()
+        return t
+
+    def samples_counts(self, x, s0=0, ns=None):
+        """int64 [nfields][nq][2]: how many window values of field f have a key below (lt) and not above (le) that of x[f][q].  Exact
+        and additive over engines that hold disjoint chains."""
+        ns, nf = self._quant_window(s0, ns)
+        xs = _f64(x)
+        if xs.ndim != 2 or xs.shape[0] != nf:
+            raise McmcError("samples_counts: x must be [nfields = %d][nq], got %s" % (nf, xs.shape))
+        a = np.zeros((nf, xs.shape[1], 2), dtype=np.int64)
+        self._chk(self.L.mcmcx_samples_counts(self.h, int(s0), ns, int(xs.shape[1]), _dp(xs), _lp(a)))
+        return a
+
+    def samples_quantiles(self, probs, s0=0, ns=None):
+        """[nfields][nq]: the quantiles at `probs` (numpy's default, linear interpolation between two order statistics) of every
+        field over the window; at most QUANT_MAXR / 2 probabilities per call."""
+        ns, nf = self._quant_window(s0, ns)
+        p = _f64(probs).ravel()
+        a = np.zeros((nf, p.size))
+        self._chk(self.L.mcmcx_samples_quantiles(self.h, int(s0), ns, int(p.size), _dp(p), _dp(a)))
+        return a
+
+    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None):
         """dict of arrays over the fields: mean, sd, rhat, ess, mcse, W, Bn, truncated; `fields` names the rows, `iterations` are the
-        window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound."""
+        window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound.  With `probs` also the
+        keys `probs` and `quantiles` ([nfields][nq], samples_quantiles of the same window)."""
         _, oldest, thin, nf = self.samples_kept()
         ns, sh = self._stats_window(s0, ns, shift)
         table = samples_diag(self.samples_stats(s0, ns, maxlag, sh), nf, maxlag)
         out = {k: table[:, j].copy() for j, k in enumerate(DIAG_COLUMNS)}
         out["fields"] = sample_field_names(self.npar, getattr(self, "nycol", 1))
         out["iterations"] = oldest + (int(s0) + np.arange(max(ns, 0), dtype=np.int64)) * thin
+        if probs is not None:
+            out["probs"] = _f64(probs).ravel().copy()
+            out["quantiles"] = self.samples_quantiles(out["probs"], s0, ns)
         return out
 
     def pooled_moments(self):
