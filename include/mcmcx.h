@@ -343,6 +343,54 @@ int mcmcx_samples_quantile_ranks(int64_t n, int32_t nq, const double *probs, int
  * (no counterpart in the reference) */
 int mcmcx_samples_quantiles(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *probs, double *host_out);
 
+/* ---- posterior covariance and correlation of the retained samples, reduced on the device where the ring lies, on the f64 matrix cores
+ * (no counterpart in the reference, whose chaincmat is one chain's adaptation state): the joint second moment of ALL chains times a
+ * window of retained samples.  Device scratch is ntiles x (nfields + nfields (nfields + 1) / 2) doubles for the tile rows (plus
+ * nfields for the shift and one vector), not a copy of the window: 195 MB at 16384 tiles and 53 fields, 170 MB at 1024 tiles and 203
+ * fields.  No sampling kernel and no state of the run is touched, so a run with these calls in the middle is the same run.  The
+ * definition is the contract -- every sum has a fixed order -- restated bit for bit in numpy by tests/cov_ref.py:
+ *   Window: retained samples s0 .. s0 + ns - 1 (ns >= 1) of ALL chains, oldest first; n = ns * nchains, held as int64_t and
+ *   returned as a double.  All nfields fields of the store are used, in the store's order.
+ *   shift_f: the caller's shift[f], or with shift == NULL field f of chain 0 in window sample 0 (mcmcx_samples_stats' rule).
+ *   z_f = x_f - shift_f, one IEEE subtraction.
+ *   Per tile T of 64 chains (lane c belongs to it when 64 T + c < nchains), for every field j and every pair j <= k, fma being the
+ *   fused multiply-add with one rounding:
+ *     s_j  = +0.0;  for each window sample w ascending, for each lane c ascending that belongs:  s_j  = s_j + z_j[w][c]
+ *     g_jk = +0.0;  for each window sample w ascending, for each lane c ascending that belongs:  g_jk = fma(z_j[w][c], z_k[w][c], g_jk)
+ *   A padding lane of the last tile contributes nothing (the kernel selects +0.0 for it, it does not multiply by zero:
+ *   fma(+0, +0, a) = a and a + 0 = a for every a these chains can hold).  This is the order in which v_mfma_f64_16x16x4_f64 adds
+ *   with the chains on its k axis, four per instruction in ascending k; s_j is the same chain against a row of ones
+ *   (fma(z, 1.0, a) = a + z).
+ *   Across tiles: the pooled moments' fixed pairwise tree (for s = 1, 2, 4, ..: v[t] += v[t + s]; no partner, no addition).
+ *   The vector, mcmcx_samples_cov_len = 1 + 2 nfields + nfields (nfields + 1) / 2 doubles:
+ *     [n, shift[nfields], S[nfields], G packed by rows of the upper triangle]
+ *   pair j <= k at j nfields - j (j - 1) / 2 + (k - j), the order of mcmcx_pooled_moments' third part.  It is additive over disjoint
+ *   chain sets that used the same shift: add n, S and G and keep the shifts; nothing collective happens here.
+ *   Finish (mcmcx_samples_cov_finish: pure host, no handle, no device; corr may be NULL), without contraction:
+ *     mean_j = shift_j + S_j / n
+ *     C_jk   = (G_jk - S_j * S_k / n) / (n - 1)     for j <= k, mirrored into the full column-major nfields x nfields matrix
+ *     corr_jk = C_jk / (sqrt(C_jj) * sqrt(C_kk))    off the diagonal;  corr_jj = 1.0 when C_jj > 0, else C_jj / (sqrt(C_jj) sqrt(C_jj))
+ *   A field that is constant over the window (sspri under a flat prior) has C_jj = 0 and gives 0 / 0 = NaN in its row and column of
+ *   corr, the diagonal included: the IEEE answer.  Non-finite samples propagate into the entries they take part in.
+ * Reading the numbers: G - S S / n cancels, and a shift far from the mean costs as many digits as (mean - shift)^2 / variance has;
+ * `mean` from mcmcx_samples_diag is a good shift (the default, one chain's value in the window, is good once the chains have met).
+ * The theta block of C is a valid mcmcx_set_cmat0 of the next run -- the reference's mcmccovf.dat cycle over all chains.
+ * mcmcx_samples_cov copies the vector to host memory and synchronises; mcmcx_samples_cov_dev writes it into the caller's DEVICE
+ * buffer, asynchronous on the engine's stream.  shift, if given, is host memory in both forms and is staged during the call.  Refused
+ * with -51 (the reason in mcmcx_last_error) on the host, before anything is launched or allocated: a null handle or output, an engine
+ * that is not inited, sampling off, ns < 1, a window outside the retained samples; the finish also refuses a null argument,
+ * nfields < 1, and an n in the vector that is below 2 or no integer.  The scratch is a buffer of its own, allocated at the first call,
+ * growing only, freed by mcmcx_destroy; if the allocation fails the size is in the message (-101). */
+/* 1 + 2 nfields + nfields (nfields + 1) / 2 (no counterpart in the reference) */
+int32_t mcmcx_samples_cov_len(mcmcx_handle h);
+/* the cov vector of the window to host memory (no counterpart in the reference) */
+int mcmcx_samples_cov(mcmcx_handle h, int32_t s0, int32_t ns, const double *shift /* [nfields] host, or NULL */, double *host_out);
+/* ... into a device buffer, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_cov_dev(mcmcx_handle h, int32_t s0, int32_t ns, const double *shift, void *dev_out);
+/* the finish: cov vector (one engine's, or the sum of several) -> mean[nfields], cov and corr column-major nfields x nfields; corr may
+ * be NULL (no counterpart in the reference) */
+int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, double *cov, double *corr);
+
 /* Pooled mode across several GPUs: at every adaptation tick the engine writes its local moment vector
  * (mcmcx_pooled_moments_len doubles) to dev_buf, synchronises its stream and calls fn(user); fn must sum dev_buf
  * over all ranks in place (an RCCL all-reduce) and return after the result is visible.  Without a hook the local
@@ -397,6 +445,12 @@ int64_t mcmcx_debug_samples_offset(int64_t slot, int64_t ntiles, int64_t nfields
  * store of one slot, one field and ceil(n / 64) tiles with n chains, out[nr] takes os(ranks[k]).  A run cannot put +-0, +-inf,
  * NaNs, denormals or values that differ in their last byte only into the ring; this can.  Refusals are -50. */
 int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int32_t nr, const int64_t *ranks, double *out);
+/* The covariance's own kernels on a caller's array (no counterpart in the reference; tests only): values[ns][nfields][nchains] host
+ * is laid out as a store of ns slots and ceil(nchains / 64) tiles, the padding lanes of the last tile filled with NaN by this entry
+ * so that the mask is exercised; out takes the cov vector.  A run cannot put NaN, inf, a forty-decade dynamic range or chosen field
+ * counts into the ring; this can.  shift: [nfields] host or NULL.  Refusals are -51. */
+int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, const double *shift,
+                            double *out);
 /* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
  * inverse != 0 the bits whose key x's bits are.  Needs no device. */
 int64_t mcmcx_debug_quant_key(double x, int32_t inverse);

@@ -127,6 +127,12 @@ SYMBOLS["mcmcx_samples_quantile_ranks"] = (C.c_int, [C.c_int64, C.c_int32, _DP, 
 SYMBOLS["mcmcx_samples_quantiles"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _DP])
 SYMBOLS["mcmcx_debug_order_stats"] = (C.c_int, [C.c_int32, C.c_int64, _DP, C.c_int32, _LP, _DP])
 SYMBOLS["mcmcx_debug_quant_key"] = (C.c_int64, [C.c_double, C.c_int32])
+# the store's posterior covariance on the matrix cores; mcmcx_samples_cov_finish is pure host
+SYMBOLS["mcmcx_samples_cov_len"] = (C.c_int32, [C.c_void_p])
+SYMBOLS["mcmcx_samples_cov"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, _DP])
+SYMBOLS["mcmcx_samples_cov_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_void_p])
+SYMBOLS["mcmcx_samples_cov_finish"] = (C.c_int, [_DP, C.c_int32, _DP, _DP, _DP])
+SYMBOLS["mcmcx_debug_samples_cov"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP])
 
 _lib = None
 

@@ -29,6 +29,7 @@
 #include "mcx_host_samples.hpp"
 #include "mcx_host_diag.hpp"
 #include "mcx_host_quant.hpp"
+#include "mcx_host_cov.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
 #include "mcx_host_callbacks.hpp"
@@ -143,6 +144,7 @@ int mcmcx_destroy(mcmcx_handle h)
     for (void *p : h->allocs) (void)hipFree(p);
     if (h->d_diag) (void)hipFree(h->d_diag);                    // the summary's scratch (mcmcx_samples_stats)
     if (h->d_quant) (void)hipFree(h->d_quant);                  // the order statistics' scratch (mcmcx_samples_order_stats)
+    if (h->d_cov) (void)hipFree(h->d_cov);                      // the covariance's scratch (mcmcx_samples_cov)
     for (void *p : h->hallocs) (void)hipHostFree(p);
     h->h_cand.release(); h->h_ev.release(); h->h_hx.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1088,6 +1090,37 @@ int mcmcx_samples_quantiles(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, 
     return 0;
 }
 
+// ------------------------------------------------------------------ the sample store's posterior covariance (mcx_host_cov.hpp)
+int32_t mcmcx_samples_cov_len(mcmcx_handle h)
+{
+    if (!h) return fail(-51, "mcmcx_samples_cov_len: null handle");
+    return (int32_t)cov_vec_len(samples_nfields(h));
+}
+
+int mcmcx_samples_cov_dev(mcmcx_handle h, int32_t s0, int32_t ns, const double *shift, void *dev_out)
+{
+    int rc = cov_check(h, s0, ns, dev_out, "mcmcx_samples_cov_dev"); if (rc) return rc;
+    return cov_engine(h, s0, ns, shift, (double *)dev_out, nullptr);
+}
+
+int mcmcx_samples_cov(mcmcx_handle h, int32_t s0, int32_t ns, const double *shift, double *host_out)
+{
+    int rc = cov_check(h, s0, ns, host_out, "mcmcx_samples_cov"); if (rc) return rc;
+    double *staged = nullptr;
+    if ((rc = cov_engine(h, s0, ns, shift, nullptr, &staged))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, staged, cov_vec_len(samples_nfields(h)) * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, double *cov, double *corr)
+{
+    if (!vec || !mean || !cov) return fail(-51, "mcmcx_samples_cov_finish: null argument");
+    if (nfields < 1) return fail(-51, "mcmcx_samples_cov_finish: nfields < 1");
+    return cov_finish(vec, nfields, mean, cov, corr);
+}
+
+
 int32_t mcmcx_pooled_moments_len(mcmcx_handle h) { return h ? 1 + h->d + h->P : -1; }
 
 static int pooled_vec_len(const mcmcx_engine *h, int kind) { return kind == 2 ? 2 + h->P : 1 + h->d + h->P + (kind == 1 ? 1 : 0); }
@@ -1275,6 +1308,39 @@ int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int
     HIPCHK(hipMemcpy(store, values, (size_t)n * 8, hipMemcpyHostToDevice));
     if ((rc = quant_select_launch(quant_window(store, 0, 1, T, 1, (int)n, 1), w, nr, ranks, dout, 0))) return rc;
     HIPCHK(hipMemcpy(out, dout, (size_t)nr * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the covariance's own kernels on a caller's array: a store of ns slots, ceil(nchains / 64) tiles and nfields fields filled from
+// values[ns][nfields][nchains]; the padding lanes of the last tile hold NaN, which a kernel that multiplied them by zero would spread
+int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, const double *shift,
+                            double *out)
+{
+    if (!values || !out) return fail(-51, "mcmcx_debug_samples_cov: null argument");
+    if (nchains < 1 || nfields < 1 || nfields > 2047 || ns < 1) return fail(-51, "mcmcx_debug_samples_cov: nchains, ns < 1 or nfields "
+        "outside 1 .. 2047");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const int T = (nchains + 63) / 64;
+    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
+    std::vector<double> host(words, std::nan(""));
+    for (int s = 0; s < ns; ++s)
+        for (int f = 0; f < nfields; ++f)
+            for (int c = 0; c < nchains; ++c)
+                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
+                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
+    DevBufs g;
+    double *store = nullptr, *w = nullptr;
+    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, cov_scratch_len(T, nfields) * 8));
+    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
+    CovArgs A;
+    A.store = store; A.shift = nullptr; A.out = nullptr; A.slot0 = 0; A.cap = (size_t)ns;
+    A.ntiles = T; A.nfields = nfields; A.nchains = nchains; A.ns = ns;
+    double *dout = w + (size_t)T * cov_row_len(nfields) + (size_t)nfields;
+    int rc = cov_launch(A, w, shift, dout, 0); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -23,6 +23,7 @@
 //   mcx_samples.hpp   samples_keep_kernel, samples_read_rows_kernel / samples_read_chains_kernel (the thinned sample store)
 //   mcx_diag.hpp      diag_tile_kernel<W>, diag_shift_kernel, diag_pack_kernel (the store's convergence summary, reduced where it lies)
 //   mcx_quant.hpp     quant_hist_kernel / quant_pick_kernel / quant_counts_kernel<NQ> (the store's order statistics and tail counts)
+//   mcx_cov.hpp       cov_tile_kernel<NS, OFF>, cov_pack_kernel (the store's posterior covariance on the f64 matrix cores)
 // The lane-GROUP kernels (16 / 4 lanes per chain, factors on chip) are mcx_group.hpp and mcx_group_ram.hpp.
 // Kernel forms that were measured and lost, or that a later form superseded, are not in the product library: tools/variants/README.md.
 #pragma once
@@ -40,3 +41,4 @@
 #include "mcx_samples.hpp"
 #include "mcx_diag.hpp"
 #include "mcx_quant.hpp"
+#include "mcx_cov.hpp"

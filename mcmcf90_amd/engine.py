@@ -83,6 +83,27 @@ def samples_diag(stats, nfields, maxlag):
     return table
 
 
+def samples_cov_len(nfields):
+    """Doubles of a cov vector: [n, shift[nfields], S[nfields], G packed by rows of the upper triangle] (mcmcx_samples_cov, include/mcmcx.h)."""
+    nf = int(nfields)
+    return 1 + 2 * nf + nf * (nf + 1) // 2
+
+
+def samples_cov_finish(vec, nfields):
+    """(mean[nfields], cov[nfields][nfields], corr[nfields][nfields]) from a cov vector (one engine's, or the sum of several engines' that
+    used the same shift): mcmcx_samples_cov_finish, pure host arithmetic, no engine and no device.  A constant field has a NaN row and
+    column in corr."""
+    L = _lib.load()
+    v = _f64(vec)
+    nf = int(nfields)
+    if v.size != samples_cov_len(nf):
+        raise McmcError("samples_cov_finish: %d doubles given, nfields %d makes %d" % (v.size, nf, samples_cov_len(nf)))
+    mean, cov, corr = np.zeros(nf), np.zeros((nf, nf)), np.zeros((nf, nf))
+    if L.mcmcx_samples_cov_finish(_dp(v), nf, _dp(mean), _dp(cov), _dp(corr)) < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return mean, cov, corr                                      # symmetric: column-major is row-major
+
+
 QUANT_MAXR = 32
 
 
@@ -507,6 +528,41 @@ class Engine:
             out["probs"] = _f64(probs).ravel().copy()
             out["quantiles"] = self.samples_quantiles(out["probs"], s0, ns)
         return out
+
+    # --- posterior covariance of the retained samples, on the matrix cores (mcmcx_samples_cov)
+    def samples_cov_stats(self, s0=0, ns=None, shift=None):
+        """The cov vector of retained samples s0 .. s0 + ns - 1 of all chains (include/mcmcx.h has the definition): additive over engines
+        that were given the same `shift`; `samples_cov_finish` finishes it."""
+        ns, sh = self._stats_window(s0, ns, shift)
+        a = np.zeros(self._chk(self.L.mcmcx_samples_cov_len(self.h)))
+        self._chk(self.L.mcmcx_samples_cov(self.h, int(s0), ns, _dp(sh), _dp(a)))
+        return a
+
+    def samples_cov_stats_torch(self, s0=0, ns=None, shift=None):
+        """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        import torch
+        ns, sh = self._stats_window(s0, ns, shift)
+        t = torch.empty(self._chk(self.L.mcmcx_samples_cov_len(self.h)), dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        self._chk(self.L.mcmcx_samples_cov_dev(self.h, int(s0), ns, _dp(sh), C.c_void_p(t.data_ptr())))
+        self.sync()
+        return t
+
+    def samples_cov(self, s0=0, ns=None, shift=None, fields="theta"):
+        """dict: `mean`, `cov`, `corr` of the window over all chains, `n` = ns x nchains, `fields` the names of the rows.  fields="theta"
+        (the default) keeps the parameter block -- its `cov` is a valid `setcmat0` of the next run --, "all" every field of the store.
+        shift="mean" first takes the mean from samples_stats(maxlag=0) (two halves: a window of four samples at least)."""
+        nf = self.samples_kept()[3]
+        if fields not in ("theta", "all"):
+            raise McmcError("samples_cov: fields must be 'theta' or 'all'")
+        if isinstance(shift, str):
+            if shift != "mean":
+                raise McmcError("samples_cov: shift must be None, 'mean' or an array")
+            shift = samples_diag(self.samples_stats(s0, ns, 0), nf, 0)[:, 0].copy()
+        vec = self.samples_cov_stats(s0, ns, shift)
+        mean, cov, corr = samples_cov_finish(vec, nf)
+        k = self.npar if fields == "theta" else nf
+        names = sample_field_names(self.npar, getattr(self, "nycol", 1))
+        return {"fields": names[:k], "mean": mean[:k].copy(), "cov": cov[:k, :k].copy(), "corr": corr[:k, :k].copy(), "n": int(vec[0])}
 
     def pooled_moments(self):
         n = self.L.mcmcx_pooled_moments_len(self.h)
