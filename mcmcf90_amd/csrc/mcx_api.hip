@@ -142,9 +142,7 @@ int mcmcx_destroy(mcmcx_handle h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto &p : h->pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (void *p : h->allocs) (void)hipFree(p);
-    if (h->d_diag) (void)hipFree(h->d_diag);                    // the summary's scratch (mcmcx_samples_stats)
-    if (h->d_quant) (void)hipFree(h->d_quant);                  // the order statistics' scratch (mcmcx_samples_order_stats)
-    if (h->d_cov) (void)hipFree(h->d_cov);                      // the covariance's scratch (mcmcx_samples_cov)
+    if (h->d_scratch) (void)hipFree(h->d_scratch);              // the scratch of the sample store's readers (samples_scratch)
     for (void *p : h->hallocs) (void)hipHostFree(p);
     h->h_cand.release(); h->h_ev.release(); h->h_hx.release();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -993,9 +991,7 @@ int mcmcx_get_samples(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, int32_
     double *tmp = nullptr;
     if (g.alloc(&tmp, bytes) != hipSuccess) return fail(-101, "mcmcx_get_samples: hipMalloc of " + std::to_string(bytes) + " bytes failed");
     if ((rc = samples_read(h, s0, ns, c0, nc, layout, tmp))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, tmp, bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return samples_fetch(h, host_out, tmp, bytes);
 }
 
 // ------------------------------------------------------------------ the sample store's convergence summary (mcx_host_diag.hpp)
@@ -1010,17 +1006,15 @@ int32_t mcmcx_samples_stats_len(mcmcx_handle h, int32_t maxlag)
 int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, void *dev_out)
 {
     int rc = diag_check(h, s0, ns, maxlag, dev_out, "mcmcx_samples_stats_dev"); if (rc) return rc;
-    return diag_launch(h, s0, ns, maxlag, shift, (double *)dev_out, nullptr);
+    return diag_engine(h, s0, ns, maxlag, shift, (double *)dev_out, nullptr);
 }
 
 int mcmcx_samples_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, double *host_out)
 {
     int rc = diag_check(h, s0, ns, maxlag, host_out, "mcmcx_samples_stats"); if (rc) return rc;
     double *staged = nullptr;
-    if ((rc = diag_launch(h, s0, ns, maxlag, shift, nullptr, &staged))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    if ((rc = diag_engine(h, s0, ns, maxlag, shift, nullptr, &staged))) return rc;
+    return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
 }
 
 int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, double *table)
@@ -1046,9 +1040,7 @@ int mcmcx_samples_order_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr
     if ((rc = quant_check_ranks((long long)ns * h->cfg.nchains, nr, ranks, "mcmcx_samples_order_stats"))) return rc;
     double *staged = nullptr;
     if ((rc = quant_order_stats(h, s0, ns, nr, ranks, nullptr, &staged))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, staged, (size_t)samples_nfields(h) * (size_t)nr * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return samples_fetch(h, host_out, staged, (size_t)samples_nfields(h) * (size_t)nr * sizeof(double));
 }
 
 int mcmcx_samples_counts_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, void *dev_out)
@@ -1062,9 +1054,7 @@ int mcmcx_samples_counts(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, con
     int rc = quant_check(h, s0, ns, nq, x, host_out, "mcmcx_samples_counts"); if (rc) return rc;
     unsigned long long *staged = nullptr;
     if ((rc = quant_counts(h, s0, ns, nq, x, nullptr, &staged))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, staged, (size_t)samples_nfields(h) * (size_t)nq * 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return 0;
+    return samples_fetch(h, host_out, staged, (size_t)samples_nfields(h) * (size_t)nq * 2 * sizeof(int64_t));
 }
 
 int mcmcx_samples_quantile_ranks(int64_t n, int32_t nq, const double *probs, int64_t *ranks, double *frac)
@@ -1108,9 +1098,7 @@ int mcmcx_samples_cov(mcmcx_handle h, int32_t s0, int32_t ns, const double *shif
     int rc = cov_check(h, s0, ns, host_out, "mcmcx_samples_cov"); if (rc) return rc;
     double *staged = nullptr;
     if ((rc = cov_engine(h, s0, ns, shift, nullptr, &staged))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, staged, cov_vec_len(samples_nfields(h)) * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return samples_fetch(h, host_out, staged, cov_vec_len(samples_nfields(h)) * sizeof(double));
 }
 
 int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, double *cov, double *corr)
@@ -1137,12 +1125,7 @@ static int pooled_moments_launch(mcmcx_engine *h, double *dev_dst, int kind, int
     // npar >= 316: (64 (d | 1) + 320) 8 bytes exceed 160 KiB (317: 164 864)
     else hipLaunchKernelGGL(moments_kernel<true>, dim3(T), dim3(256), (size_t)320 * sizeof(double), h->stream, h->E, h->d_moments,
         h->cfg.nchains, kind, it, rs);
-    for (long long stride = 1;; stride *= 64) {                            // six levels of the fixed pairwise tree per launch
-        const long long groups = (T + 64 * stride - 1) / (64 * stride);
-        hipLaunchKernelGGL(moments_tree_kernel, dim3((len + 255) / 256, (unsigned)groups), dim3(256), 0, h->stream, h->d_moments, T, len,
-                           (int)stride, dev_dst);
-        if (groups == 1) break;
-    }
+    moments_tree_launch(h->stream, h->d_moments, T, len, dev_dst);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1306,7 +1289,8 @@ int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int
     HIPCHK(g.alloc(&w, quant_select_words(1, nr) * sizeof(unsigned long long)));
     HIPCHK(hipMemset(store, 0xFF, (size_t)T * 512));
     HIPCHK(hipMemcpy(store, values, (size_t)n * 8, hipMemcpyHostToDevice));
-    if ((rc = quant_select_launch(quant_window(store, 0, 1, T, 1, (int)n, 1), w, nr, ranks, dout, 0))) return rc;
+    const SampleWin W = {store, 0, 1, T, 1, (int)n, 1};         // one slot, one field
+    if ((rc = quant_select_launch(quant_window(W), w, nr, ranks, dout, 0))) return rc;
     HIPCHK(hipMemcpy(out, dout, (size_t)nr * 8, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1334,11 +1318,9 @@ int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, in
     double *store = nullptr, *w = nullptr;
     HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, cov_scratch_len(T, nfields) * 8));
     HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
-    CovArgs A;
-    A.store = store; A.shift = nullptr; A.out = nullptr; A.slot0 = 0; A.cap = (size_t)ns;
-    A.ntiles = T; A.nfields = nfields; A.nchains = nchains; A.ns = ns;
+    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
     double *dout = w + (size_t)T * cov_row_len(nfields) + (size_t)nfields;
-    int rc = cov_launch(A, w, shift, dout, 0); if (rc) return rc;
+    int rc = cov_launch(W, w, shift, dout, 0); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(0));
     HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
     return 0;

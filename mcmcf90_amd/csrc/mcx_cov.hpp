@@ -35,6 +35,8 @@ namespace mcx {
 
 constexpr int COV_LD = 65;          // doubles per staged row: 64 chains + 1 of padding
 
+// the window's members one by one, like DiagArgs and for its reason: with a SampleWin as one member every cov_tile_kernel instantiation
+// loads its arguments in other groups and allocates other scalar registers
 struct CovArgs {
     const double *store; const double *shift; double *out;      // the ring; shift[nfields]; out[ntiles][nf + nf (nf + 1) / 2]
     size_t slot0, cap;                                          // ring slot of window sample 0, the ring's capacity
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(64) void cov_tile_kernel(CovArgs A)
         asm volatile("" : "+s"(nfo));
 #pragma unroll
         for (int s = 0; s < NS; ++s) { bo[s] = blk[s]; asm volatile("" : "+s"(bo[s])); }
-        const double *p = A.store + samples_row(diag_slot(A.slot0, w, A.cap), (size_t)A.ntiles, (size_t)nf, tile, 0) + lane;
+        const double *p = A.store + samples_row(samples_slot(A.slot0, w, A.cap), (size_t)A.ntiles, (size_t)nf, tile, 0) + lane;
 #pragma unroll
         for (int r = 0; r < NR; ++r) { const int f = 16 * bo[r >> 4] + (r & 15); v[r] = p[(size_t)(f < nfo ? f : nfo - 1) * 64]; }
     };

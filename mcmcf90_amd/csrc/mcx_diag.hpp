@@ -24,19 +24,14 @@ namespace mcx {
 constexpr int DIAG_MAXLAG = 32;     // = MCMCX_DIAG_MAXLAG
 constexpr int DIAG_LB = 8;          // rows a wave has in flight
 
+// The window's members (a SampleWin's, mcx_samples.hpp) stand here one by one, filled from one by diag_launch on the host: with the window
+// as ONE member the argument block is laid out and loaded differently, and diag_tile_kernel<W> compiles to other scalar code (six
+// instructions fewer, two scalar registers more at W = 33) -- the kernel is the definition's bits and stays the instructions it was
 struct DiagArgs {
     const double *store; const double *shift; double *out;      // the ring; shift[nfields]; out[ntiles][nfields][maxlag + 3]
     size_t slot0, cap;                                          // ring slot of window sample 0, the ring's capacity
     int ntiles, nfields, nchains, ns, nh, K, maxlag;
 };
-
-// ring slot of window sample w: (slot0 + w) % cap as in samples_read, for slot0 < cap and w < cap (a window is never longer than the ring)
-// -- without the 64-bit division the % would cost every row
-MCX_DEV size_t diag_slot(size_t slot0, int w, size_t cap)
-{
-    const size_t q = slot0 + (size_t)w;
-    return q >= cap ? q - cap : q;
-}
 
 // Samples j0 .. j0 + B - 1 of a half (those below n): z_j = (x_j - shift) - m enters the window at j % W and every lag sum takes its
 // product, a_t = a_t + z_{j-t} z_j -- g_t's terms in g_t's order (i = j - t ascending; the product commutes).  HEAD: the half's first
@@ -88,7 +83,7 @@ __global__ __launch_bounds__(256) void diag_tile_kernel(DiagArgs A)
         asm volatile("" : "+s"(n));
         const int w0 = h ? A.ns - n : 0;
         auto row = [&](int i) {
-            return A.store + samples_row(diag_slot(A.slot0, w0 + i, A.cap), (size_t)A.ntiles, (size_t)A.nfields, tile, (size_t)f) + lane;
+            return A.store + samples_row(samples_slot(A.slot0, w0 + i, A.cap), (size_t)A.ntiles, (size_t)A.nfields, tile, (size_t)f) + lane;
         };
         double s = -0.0;
         for (int j0 = 0; j0 < n; j0 += DIAG_LB) {

@@ -1,6 +1,6 @@
 // mcx_host_cov.hpp -- the sample store's posterior covariance, host side (mcmcx_samples_cov / _dev / _finish, mcmcx_debug_samples_cov):
-// the window checks, the tile scratch, the launches of mcx_cov.hpp's kernels, of diag_shift_kernel and of moments_tree_kernel, and the
-// finish -- pure host arithmetic on a cov vector.
+// its own refusals, its layout of the readers' scratch, the launches of mcx_cov.hpp's kernels, and the finish -- pure host arithmetic on
+// a cov vector.  The window, the scratch, the shift and the tree launch are mcx_host_samples.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_quant.hpp); not a stand-alone header.
 
 static size_t cov_row_len(int nfields) { return (size_t)nfields + (size_t)nfields * (size_t)(nfields + 1) / 2; }
@@ -16,39 +16,20 @@ static int cov_check(mcmcx_engine *h, int s0, int ns, const void *out, const cha
 {
     if (!h) return fail(-51, std::string(who) + ": null handle");
     if (!out) return fail(-51, std::string(who) + ": null output");
-    if (!h->inited) return fail(-51, std::string(who) + ": we have not inited");
-    if (h->samp.thin <= 0) return fail(-51, std::string(who) + ": no samples are kept (mcmcx_set_samples before mcmcx_init)");
-    if (ns < 1) return fail(-51, std::string(who) + ": a window of " + std::to_string(ns) + " samples");
-    const long long have = samples_retained(h);
-    if (s0 < 0 || (long long)s0 + ns > have) return fail(-51, std::string(who) + ": samples " + std::to_string(s0) + " .. " +
-        std::to_string((long long)s0 + ns - 1) + " asked for, " + std::to_string(have) + " retained");
-    return 0;
+    return samples_window_check(h, s0, ns, -51, 1, who);
 }
 
-// allocated at the first call, grows only, freed by mcmcx_destroy
-static int cov_scratch(mcmcx_engine *h, size_t need)
+// The cov vector of window W (scratch w of cov_scratch_len doubles) into dev_out; asynchronous on `stream`.  shift: host memory or
+// nullptr (chain 0 of window sample 0).
+static int cov_launch(const SampleWin &W, double *w, const double *shift, double *dev_out, hipStream_t stream)
 {
-    if (need <= h->cov_cap) return 0;
-    HIPCHK(hipStreamSynchronize(h->stream));                    // an earlier call may still read the old one
-    if (h->d_cov) (void)hipFree(h->d_cov);
-    h->d_cov = nullptr; h->cov_cap = 0;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, need * sizeof(double));
-    if (e != hipSuccess) return fail(-101, "hipMalloc of " + std::to_string(need * sizeof(double)) + " bytes: " + hipGetErrorString(e));
-    h->d_cov = (double *)q; h->cov_cap = need;
-    return 0;
-}
-
-// The cov vector of window A (A.out: the tile rows of a scratch w of cov_scratch_len doubles, A.shift: its shift) into dev_out;
-// asynchronous on `stream`.  shift: host memory or nullptr (chain 0 of window sample 0).
-static int cov_launch(CovArgs A, double *w, const double *shift, double *dev_out, hipStream_t stream)
-{
-    const int nf = A.nfields, T = A.ntiles;
+    const int nf = W.nfields, T = W.ntiles;
     const size_t len = cov_row_len(nf);
     double *rows = w, *dshift = rows + (size_t)T * len;
-    A.out = rows; A.shift = dshift;
-    if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, stream));
-    else hipLaunchKernelGGL(diag_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, A.store, dshift, A.slot0, T, nf);
+    int rc = samples_shift(W, shift, dshift, stream); if (rc) return rc;
+    CovArgs A;
+    A.store = W.store; A.shift = dshift; A.out = rows; A.slot0 = W.slot0; A.cap = W.cap;
+    A.ntiles = T; A.nfields = nf; A.nchains = W.nchains; A.ns = W.ns;
     const int nblk = (nf + 1 + 15) / 16;                        // 16-row blocks of the fields and the row of ones
     const dim3 block(64);
     if (nblk <= 4) {                                            // form A: the whole upper block triangle in one wave
@@ -63,16 +44,10 @@ static int cov_launch(CovArgs A, double *w, const double *shift, double *dev_out
         hipLaunchKernelGGL((cov_tile_kernel<4, true>), dim3((unsigned)T, (unsigned)(nsup * (nsup - 1) / 2)), block, 0, stream, A);
     }
     // the length is a size_t at real sizes only in bytes: nfields <= 2047 keeps it an int (the store's nfields is far below)
-    const int ilen = (int)len;
-    for (long long stride = 1;; stride *= 64) {                 // as pooled_moments_launch does
-        const long long groups = (T + 64 * stride - 1) / (64 * stride);
-        hipLaunchKernelGGL(moments_tree_kernel, dim3((unsigned)((ilen + 255) / 256), (unsigned)groups), dim3(256), 0, stream, rows, T, ilen,
-                           (int)stride, (double *)nullptr);
-        if (groups == 1) break;
-    }
-    const int vlen = (int)cov_vec_len(nf);
+    const int ilen = (int)len, vlen = (int)cov_vec_len(nf);
+    moments_tree_launch(stream, rows, T, ilen, nullptr);
     hipLaunchKernelGGL(cov_pack_kernel, dim3((unsigned)((vlen + 255) / 256)), dim3(256), 0, stream, (const double *)rows,
-        (const double *)dshift, dev_out, nf, ilen, (double)((int64_t)A.ns * (int64_t)A.nchains));
+        (const double *)dshift, dev_out, nf, ilen, (double)((int64_t)W.ns * (int64_t)W.nchains));
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -80,18 +55,14 @@ static int cov_launch(CovArgs A, double *w, const double *shift, double *dev_out
 // the cov vector of the engine's window into dev_out (nullptr: the scratch's staging vector, returned in *staged)
 static int cov_engine(mcmcx_engine *h, int s0, int ns, const double *shift, double *dev_out, double **staged)
 {
-    const SamplePlan &s = h->samp;
     HIPCHK(hipSetDevice(h->cfg.device));
-    const int nf = samples_nfields(h), T = h->ntiles;
-    int rc = cov_scratch(h, cov_scratch_len(T, nf)); if (rc) return rc;
-    if (!dev_out) dev_out = h->d_cov + (size_t)T * cov_row_len(nf) + (size_t)nf;
+    const SampleWin W = samples_window(h, s0, ns);
+    const size_t need = cov_scratch_len(W.ntiles, W.nfields);
+    int rc = samples_scratch(h, need * sizeof(double)); if (rc) return rc;
+    double *w = (double *)h->d_scratch;
+    if (!dev_out) dev_out = w + need - cov_vec_len(W.nfields);
     if (staged) *staged = dev_out;
-    const long long have = samples_retained(h);
-    CovArgs A;
-    A.store = s.store; A.shift = nullptr; A.out = nullptr;
-    A.slot0 = (size_t)((s.kept - have + s0) % s.capacity); A.cap = (size_t)s.capacity;
-    A.ntiles = T; A.nfields = nf; A.nchains = h->cfg.nchains; A.ns = ns;
-    return cov_launch(A, h->d_cov, shift, dev_out, h->stream);
+    return cov_launch(W, w, shift, dev_out, h->stream);
 }
 
 // The finish (include/mcmcx.h states it): mean[nf], cov and corr column-major nf x nf (corr may be null)

@@ -1,8 +1,14 @@
-// mcx_host_diag.hpp -- the sample store's convergence summary, host side (mcmcx_samples_stats / _dev / _diag): the window checks, the tile
-// scratch, the launches of mcx_diag.hpp's kernels and of moments_tree_kernel, and the finish -- pure host arithmetic on a stats vector.
+// mcx_host_diag.hpp -- the sample store's convergence summary, host side (mcmcx_samples_stats / _dev / _diag): its own refusals, its layout
+// of the readers' scratch, the launches of mcx_diag.hpp's kernels, and the finish -- pure host arithmetic on a stats vector.  The window,
+// the scratch, the shift and the tree launch are mcx_host_samples.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_samples.hpp); not a stand-alone header.
 
 static int diag_stats_len(int nfields, int maxlag) { return 3 + nfields * (maxlag + 4); }
+// doubles of the scratch: [ntiles][nfields][maxlag + 3] tile rows, shift[nfields], one stats vector (the host form's staging)
+static size_t diag_scratch_len(int ntiles, int nfields, int maxlag)
+{
+    return (size_t)ntiles * (size_t)nfields * (size_t)(maxlag + 3) + (size_t)nfields + (size_t)diag_stats_len(nfields, maxlag);
+}
 
 // every refusal is -49, on the host, before anything is launched or allocated
 static int diag_check(mcmcx_engine *h, int s0, int ns, int maxlag, const void *out, const char *who)
@@ -11,65 +17,44 @@ static int diag_check(mcmcx_engine *h, int s0, int ns, int maxlag, const void *o
     if (!out) return fail(-49, std::string(who) + ": null output");
     if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-49, std::string(who) + ": maxlag " + std::to_string(maxlag) +
         " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
-    if (!h->inited) return fail(-49, std::string(who) + ": we have not inited");
-    if (h->samp.thin <= 0) return fail(-49, std::string(who) + ": no samples are kept (mcmcx_set_samples before mcmcx_init)");
-    if (ns < 4) return fail(-49, std::string(who) + ": a window of " + std::to_string(ns) + " samples (two halves of two need 4)");
-    const long long have = samples_retained(h);
-    if (s0 < 0 || (long long)s0 + ns > have) return fail(-49, std::string(who) + ": samples " + std::to_string(s0) + " .. " +
-        std::to_string((long long)s0 + ns - 1) + " asked for, " + std::to_string(have) + " retained");
-    return 0;
+    return samples_window_check(h, s0, ns, -49, 4, who);       // two halves of two samples
 }
 
-// the scratch: [ntiles][nfields][maxlag + 3] tile rows, shift[nfields], one stats vector (the host form's staging); allocated at the first
-// call, grows only, freed by mcmcx_destroy
-static int diag_scratch(mcmcx_engine *h, size_t need)
+// The stats vector of window W (scratch w of diag_scratch_len doubles) into dev_out; asynchronous on `stream`.  shift: host memory or
+// nullptr (chain 0 of window sample 0).
+static int diag_launch(const SampleWin &W, double *w, int maxlag, const double *shift, double *dev_out, hipStream_t stream)
 {
-    if (need <= h->diag_cap) return 0;
-    HIPCHK(hipStreamSynchronize(h->stream));                    // an earlier summary may still read the old one
-    if (h->d_diag) (void)hipFree(h->d_diag);
-    h->d_diag = nullptr; h->diag_cap = 0;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, need * sizeof(double));
-    if (e != hipSuccess) return fail(-101, "hipMalloc of " + std::to_string(need * sizeof(double)) + " bytes: " + hipGetErrorString(e));
-    h->d_diag = (double *)q; h->diag_cap = need;
-    return 0;
-}
-
-// the stats vector of the window into dev_out (nullptr: the scratch's staging vector, returned in *staged); asynchronous on the stream
-static int diag_launch(mcmcx_engine *h, int s0, int ns, int maxlag, const double *shift, double *dev_out, double **staged)
-{
-    const SamplePlan &s = h->samp;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const int nf = samples_nfields(h), T = h->ntiles, nh = ns / 2, K = std::min(maxlag, nh - 1);
+    const int nf = W.nfields, T = W.ntiles, nh = W.ns / 2, K = std::min(maxlag, nh - 1);
     const int len = nf * (maxlag + 3), slen = diag_stats_len(nf, maxlag);
-    int rc = diag_scratch(h, (size_t)T * (size_t)len + (size_t)nf + (size_t)slen); if (rc) return rc;
-    double *rows = h->d_diag, *dshift = rows + (size_t)T * (size_t)len, *stage = dshift + nf;
-    if (!dev_out) dev_out = stage;
-    if (staged) *staged = dev_out;
-    const long long have = samples_retained(h);
-    const size_t slot0 = (size_t)((s.kept - have + s0) % s.capacity);
-    if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    else hipLaunchKernelGGL(diag_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, h->stream, (const double *)s.store, dshift,
-        slot0, T, nf);
+    double *rows = w, *dshift = rows + (size_t)T * (size_t)len;
+    int rc = samples_shift(W, shift, dshift, stream); if (rc) return rc;
     DiagArgs A;
-    A.store = s.store; A.shift = dshift; A.out = rows; A.slot0 = slot0; A.cap = (size_t)s.capacity;
-    A.ntiles = T; A.nfields = nf; A.nchains = h->cfg.nchains; A.ns = ns; A.nh = nh; A.K = K; A.maxlag = maxlag;
+    A.store = W.store; A.shift = dshift; A.out = rows; A.slot0 = W.slot0; A.cap = W.cap;
+    A.ntiles = T; A.nfields = nf; A.nchains = W.nchains; A.ns = W.ns; A.nh = nh; A.K = K; A.maxlag = maxlag;
     const dim3 grid((unsigned)T, (unsigned)((nf + 3) / 4)), block(256);
     // the window length W of the instantiation holds lags 0 .. W - 1 >= K
-    if (K == 0) hipLaunchKernelGGL(diag_tile_kernel<1>, grid, block, 0, h->stream, A);
-    else if (K <= 8) hipLaunchKernelGGL(diag_tile_kernel<9>, grid, block, 0, h->stream, A);
-    else if (K <= 16) hipLaunchKernelGGL(diag_tile_kernel<17>, grid, block, 0, h->stream, A);
-    else hipLaunchKernelGGL(diag_tile_kernel<33>, grid, block, 0, h->stream, A);
-    for (long long stride = 1;; stride *= 64) {                            // as pooled_moments_launch does
-        const long long groups = (T + 64 * stride - 1) / (64 * stride);
-        hipLaunchKernelGGL(moments_tree_kernel, dim3((unsigned)((len + 255) / 256), (unsigned)groups), dim3(256), 0, h->stream, rows, T,
-                           len, (int)stride, (double *)nullptr);
-        if (groups == 1) break;
-    }
-    hipLaunchKernelGGL(diag_pack_kernel, dim3((unsigned)((slen + 255) / 256)), dim3(256), 0, h->stream, (const double *)rows,
-        (const double *)dshift, dev_out, nf, maxlag, 2.0 * (double)h->cfg.nchains, (double)nh, (double)K);
+    if (K == 0) hipLaunchKernelGGL(diag_tile_kernel<1>, grid, block, 0, stream, A);
+    else if (K <= 8) hipLaunchKernelGGL(diag_tile_kernel<9>, grid, block, 0, stream, A);
+    else if (K <= 16) hipLaunchKernelGGL(diag_tile_kernel<17>, grid, block, 0, stream, A);
+    else hipLaunchKernelGGL(diag_tile_kernel<33>, grid, block, 0, stream, A);
+    moments_tree_launch(stream, rows, T, len, nullptr);
+    hipLaunchKernelGGL(diag_pack_kernel, dim3((unsigned)((slen + 255) / 256)), dim3(256), 0, stream, (const double *)rows,
+        (const double *)dshift, dev_out, nf, maxlag, 2.0 * (double)W.nchains, (double)nh, (double)K);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// the stats vector of the engine's window into dev_out (nullptr: the scratch's staging vector, returned in *staged)
+static int diag_engine(mcmcx_engine *h, int s0, int ns, int maxlag, const double *shift, double *dev_out, double **staged)
+{
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const SampleWin W = samples_window(h, s0, ns);
+    const size_t need = diag_scratch_len(W.ntiles, W.nfields, maxlag);
+    int rc = samples_scratch(h, need * sizeof(double)); if (rc) return rc;
+    double *w = (double *)h->d_scratch;
+    if (!dev_out) dev_out = w + need - (size_t)diag_stats_len(W.nfields, maxlag);
+    if (staged) *staged = dev_out;
+    return diag_launch(W, w, maxlag, shift, dev_out, h->stream);
 }
 
 // The finish (include/mcmcx.h states it): table[f] = mean, sd, rhat, ess, mcse, W, Bn, truncated

@@ -176,9 +176,7 @@ struct mcmcx_engine {
     EngineDev E{};
     std::vector<void *> allocs;
     double *d_ramscale = nullptr, *d_moments = nullptr;
-    double *d_diag = nullptr; size_t diag_cap = 0;    // scratch of the sample store's summary (mcx_host_diag.hpp): first call, grows only
-    unsigned long long *d_quant = nullptr; size_t quant_cap = 0;   // ... of its order statistics and counts (mcx_host_quant.hpp): likewise
-    double *d_cov = nullptr; size_t cov_cap = 0;      // ... of its posterior covariance (mcx_host_cov.hpp): likewise
+    void *d_scratch = nullptr; size_t scratch_cap = 0;  // the sample store's readers' scratch, in bytes (samples_scratch): grows only
     // blocked SVD of the adaptation (large npar)
     double *d_Gc = nullptr, *d_Vc = nullptr, *d_svc = nullptr; uint8_t *d_need = nullptr, *d_state = nullptr; int *d_anyrot = nullptr;
     int wcap = 0;

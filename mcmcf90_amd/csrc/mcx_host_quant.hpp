@@ -1,5 +1,6 @@
 // mcx_host_quant.hpp -- exact order statistics, tail counts and quantiles of the sample store, host side (mcmcx_samples_order_stats /
-// _counts / _quantile_ranks / _quantiles): the window checks, the scratch, the launches of mcx_quant.hpp's kernels, the quantile's finish.
+// _counts / _quantile_ranks / _quantiles): its own refusals, its layouts of the readers' scratch, the launches of mcx_quant.hpp's kernels,
+// the quantile's finish.  The window and the scratch are mcx_host_samples.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_diag.hpp); not a stand-alone header.
 
 // every refusal is -50, on the host, before anything is launched or allocated (nr: the number of ranks or thresholds).  What the
@@ -11,13 +12,7 @@ static int quant_check(mcmcx_engine *h, int s0, int ns, int nr, const void *arg,
     if (nr < 1 || nr > MCMCX_QUANT_MAXR) return fail(-50, std::string(who) + ": " + std::to_string(nr) +
         " ranks or thresholds, outside 1 .. " + std::to_string(MCMCX_QUANT_MAXR));
     if (!h) return fail(-50, std::string(who) + ": null handle");
-    if (!h->inited) return fail(-50, std::string(who) + ": we have not inited");
-    if (h->samp.thin <= 0) return fail(-50, std::string(who) + ": no samples are kept (mcmcx_set_samples before mcmcx_init)");
-    if (ns < 1) return fail(-50, std::string(who) + ": a window of " + std::to_string(ns) + " samples");
-    const long long have = samples_retained(h);
-    if (s0 < 0 || (long long)s0 + ns > have) return fail(-50, std::string(who) + ": samples " + std::to_string(s0) + " .. " +
-        std::to_string((long long)s0 + ns - 1) + " asked for, " + std::to_string(have) + " retained");
-    return 0;
+    return samples_window_check(h, s0, ns, -50, 1, who);
 }
 
 static int quant_check_ranks(long long n, int nr, const int64_t *ranks, const char *who)
@@ -32,35 +27,11 @@ static int quant_check_ranks(long long n, int nr, const int64_t *ranks, const ch
 static size_t quant_select_words(int nf, int nr) { return (size_t)nf * (size_t)nr * (size_t)(QUANT_NB + 4); }
 static size_t quant_counts_words(int nf, int nq) { return (size_t)nf * (size_t)nq * 3; }
 
-// allocated at the first call, grows only, freed by mcmcx_destroy
-static int quant_scratch(mcmcx_engine *h, size_t need)
-{
-    if (need <= h->quant_cap) return 0;
-    HIPCHK(hipStreamSynchronize(h->stream));                    // an earlier call may still use the old one
-    if (h->d_quant) (void)hipFree(h->d_quant);
-    h->d_quant = nullptr; h->quant_cap = 0;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, need * sizeof(unsigned long long));
-    if (e != hipSuccess) return fail(-101, "hipMalloc of " + std::to_string(need * sizeof(unsigned long long)) + " bytes: " +
-        hipGetErrorString(e));
-    h->d_quant = (unsigned long long *)q; h->quant_cap = need;
-    return 0;
-}
-
-static QuantWin quant_window(const double *store, size_t slot0, size_t cap, int ntiles, int nfields, int nchains, int ns)
+static QuantWin quant_window(const SampleWin &W)
 {
     QuantWin A;
-    A.store = store; A.slot0 = slot0; A.cap = cap; A.ntiles = ntiles; A.nfields = nfields; A.nchains = nchains; A.ns = ns;
-    A.chunk = std::min(ns, 65536);
+    A.win = W; A.chunk = std::min(W.ns, 65536);
     return A;
-}
-
-static QuantWin quant_engine_window(mcmcx_engine *h, int s0, int ns)
-{
-    const SamplePlan &s = h->samp;
-    const long long have = samples_retained(h);
-    return quant_window(s.store, (size_t)((s.kept - have + s0) % s.capacity), (size_t)s.capacity, h->ntiles, samples_nfields(h),
-        h->cfg.nchains, ns);
 }
 
 // The select of nr ranks per field over window A with scratch `w` (quant_select_words), the result into dev_out[nfields][nr];
@@ -68,7 +39,7 @@ static QuantWin quant_engine_window(mcmcx_engine *h, int s0, int ns)
 // never more than 65 536 window samples of them -- 2**31 values, so that a 32-bit counter in LDS cannot wrap whatever n is.
 static int quant_select_launch(const QuantWin &A, unsigned long long *w, int nr, const int64_t *ranks, double *dev_out, hipStream_t stream)
 {
-    const int nf = A.nfields, T = A.ntiles;
+    const int nf = A.win.nfields, T = A.win.ntiles;
     const size_t m = (size_t)nf * (size_t)nr;
     QuantState S;
     S.table = w; S.prefix = w + m * QUANT_NB; S.rest = S.prefix + m; S.leader = S.rest + m; S.nr = nr;
@@ -76,7 +47,7 @@ static int quant_select_launch(const QuantWin &A, unsigned long long *w, int nr,
     for (int k = 0; k < QUANT_MAXR; ++k) R.r[k] = k < nr ? (long long)ranks[k] : 0;
     const long long t4 = ((long long)T + 3) / 4;
     const long long gx = std::min(t4, std::max<long long>(std::max(1, 2560 / nf), (t4 + 127) / 128));
-    const dim3 grid((unsigned)gx, (unsigned)nf, (unsigned)((A.ns + A.chunk - 1) / A.chunk)), block(256);
+    const dim3 grid((unsigned)gx, (unsigned)nf, (unsigned)((A.win.ns + A.chunk - 1) / A.chunk)), block(256);
     const size_t lds = (size_t)nr * QUANT_NB * sizeof(unsigned int);
     hipLaunchKernelGGL(quant_init_kernel, dim3((unsigned)((m * QUANT_NB + 255) / 256)), block, 0, stream, S, R, nf);
     for (int sh = 64 - QUANT_B; sh >= 0; sh -= QUANT_B) {
@@ -92,10 +63,11 @@ static int quant_order_stats(mcmcx_engine *h, int s0, int ns, int nr, const int6
 {
     HIPCHK(hipSetDevice(h->cfg.device));
     const int nf = samples_nfields(h);
-    int rc = quant_scratch(h, quant_select_words(nf, nr)); if (rc) return rc;
-    if (!dev_out) dev_out = (double *)(h->d_quant + (size_t)nf * (size_t)nr * (size_t)(QUANT_NB + 3));
+    int rc = samples_scratch(h, quant_select_words(nf, nr) * sizeof(unsigned long long)); if (rc) return rc;
+    unsigned long long *w = (unsigned long long *)h->d_scratch;
+    if (!dev_out) dev_out = (double *)(w + (size_t)nf * (size_t)nr * (size_t)(QUANT_NB + 3));
     if (staged) *staged = dev_out;
-    return quant_select_launch(quant_engine_window(h, s0, ns), h->d_quant, nr, ranks, dev_out, h->stream);
+    return quant_select_launch(quant_window(samples_window(h, s0, ns)), w, nr, ranks, dev_out, h->stream);
 }
 
 // lt / le of nq thresholds per field (x[nfields][nq], host) into dev_out[nfields][nq][2] (nullptr: the scratch's own); asynchronous
@@ -104,15 +76,15 @@ static int quant_counts(mcmcx_engine *h, int s0, int ns, int nq, const double *x
     HIPCHK(hipSetDevice(h->cfg.device));
     const int nf = samples_nfields(h), T = h->ntiles;
     const size_t m = (size_t)nf * (size_t)nq;
-    int rc = quant_scratch(h, quant_counts_words(nf, nq)); if (rc) return rc;
-    unsigned long long *xkey = h->d_quant + 2 * m;
-    if (!dev_out) dev_out = h->d_quant;
+    int rc = samples_scratch(h, quant_counts_words(nf, nq) * sizeof(unsigned long long)); if (rc) return rc;
+    unsigned long long *w = (unsigned long long *)h->d_scratch, *xkey = w + 2 * m;
+    if (!dev_out) dev_out = w;
     if (staged) *staged = dev_out;
     std::vector<unsigned long long> keys(m);
     for (size_t i = 0; i < m; ++i) { unsigned long long b; memcpy(&b, x + i, 8); keys[i] = quant_key(b); }
     // from pageable memory the copy is staged before it returns: `keys` and x need only live until then
     HIPCHK(hipMemcpyAsync(xkey, keys.data(), m * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
-    const QuantWin A = quant_engine_window(h, s0, ns);
+    const QuantWin A = quant_window(samples_window(h, s0, ns));
     const int fb = (nf + 3) / 4;
     const long long gx = std::min<long long>(T, std::max<long long>(std::max(1, 2560 / fb), ((long long)T + 32767) / 32768));
     const dim3 grid((unsigned)gx, (unsigned)fb, (unsigned)((ns + A.chunk - 1) / A.chunk)), block(256);

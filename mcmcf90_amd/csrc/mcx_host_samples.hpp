@@ -1,5 +1,7 @@
 // mcx_host_samples.hpp -- the thinned sample store's host side (mcmcx_set_samples): the rule, the store's allocation, the keep between two
-// launches, the window checks and launches of the two read kernels (mcx_samples.hpp).
+// launches, the window checks and launches of the two read kernels (mcx_samples.hpp) -- and what every reader of the ring shares
+// (mcx_host_diag.hpp, mcx_host_quant.hpp, mcx_host_cov.hpp): the window as a launch argument, its refusals, the one scratch, the default
+// shift, the launch of the pooled moment tree and the host form of a staged result.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_launch.hpp); not a stand-alone header.
 
 // Iteration it is kept: a function of the configuration alone -- the same on every rank, no collective behind it.  thin = 0: never.
@@ -36,18 +38,40 @@ static int samples_keep(mcmcx_engine *h, int it)
 
 static long long samples_retained(const mcmcx_engine *h) { return std::min<long long>(h->samp.kept, h->samp.capacity); }
 
+// The window of retained samples s0 .. s0 + ns - 1 as the readers' launch argument: the ONE place that knows where it lies in the ring
+static SampleWin samples_window(const mcmcx_engine *h, int s0, int ns)
+{
+    const SamplePlan &s = h->samp;
+    SampleWin W;
+    W.store = s.store; W.slot0 = (size_t)((s.kept - samples_retained(h) + s0) % s.capacity); W.cap = (size_t)s.capacity;
+    W.ntiles = h->ntiles; W.nfields = samples_nfields(h); W.nchains = h->cfg.nchains; W.ns = ns;
+    return W;
+}
+
+// The refusals of a window that every reader shares, after its own (`code`: the reader's refusal code, min_ns: its shortest window), on the
+// host, before anything is launched or allocated.  h is not null.
+static int samples_window_check(const mcmcx_engine *h, int s0, int ns, int code, int min_ns, const char *who)
+{
+    if (!h->inited) return fail(code, std::string(who) + ": we have not inited");
+    if (h->samp.thin <= 0) return fail(code, std::string(who) + ": no samples are kept (mcmcx_set_samples before mcmcx_init)");
+    if (ns < min_ns) return fail(code, std::string(who) + ": a window of " + std::to_string(ns) + " samples, " + std::to_string(min_ns) +
+        " at least");
+    const long long have = samples_retained(h);
+    if (s0 < 0 || (long long)s0 + ns > have) return fail(code, std::string(who) + ": samples " + std::to_string(s0) + " .. " +
+        std::to_string((long long)s0 + ns - 1) + " asked for, " + std::to_string(have) + " retained");
+    return 0;
+}
+
 // a getter's window: retained samples s0 .. s0 + ns - 1 of chains c0 .. c0 + nc - 1 (checked on the host, before any launch)
 static int samples_check(mcmcx_engine *h, int s0, int ns, int c0, int nc, int layout, const void *out, const char *who)
 {
     if (!h) return fail(-1, "null handle");
     if (!h->inited) return fail(-40, "we have not inited");
     if (!out) return fail(-1, std::string(who) + ": null argument");
-    const SamplePlan &s = h->samp;
-    const long long have = samples_retained(h);
-    if (s.thin <= 0) return fail(-48, std::string(who) + ": no samples are kept (mcmcx_set_samples before mcmcx_init)");
-    if (layout != 0 && layout != 1) return fail(-48, std::string(who) + ": layout must be 0 ([ns][nc][nfields]) or 1 ([ns][nfields][nc])");
-    if (s0 < 0 || ns < 1 || (long long)s0 + ns > have) return fail(-48, std::string(who) + ": samples " + std::to_string(s0) + " .. " +
-        std::to_string((long long)s0 + ns - 1) + " asked for, " + std::to_string(have) + " retained");
+    // (a store that keeps nothing is refused before the layout is looked at)
+    if (h->samp.thin > 0 && layout != 0 && layout != 1) return fail(-48, std::string(who) + ": layout must be 0 ([ns][nc][nfields]) or 1 "
+        "([ns][nfields][nc])");
+    int rc = samples_window_check(h, s0, ns, -48, 1, who); if (rc) return rc;
     if (c0 < 0 || nc < 1 || (long long)c0 + nc > h->cfg.nchains) return fail(-48, std::string(who) + ": chains " + std::to_string(c0) +
         " .. " + std::to_string((long long)c0 + nc - 1) + " asked for, nchains = " + std::to_string(h->cfg.nchains));
     return 0;
@@ -56,17 +80,65 @@ static int samples_check(mcmcx_engine *h, int s0, int ns, int c0, int nc, int la
 // ... into dev_out ([ns][nc][nfields] or [ns][nfields][nc] doubles), asynchronous on the engine's stream
 static int samples_read(mcmcx_engine *h, int s0, int ns, int c0, int nc, int layout, double *dev_out)
 {
-    const SamplePlan &s = h->samp;
-    const long long have = samples_retained(h);
     HIPCHK(hipSetDevice(h->cfg.device));
-    const int nf = samples_nfields(h);
+    const SampleWin W = samples_window(h, s0, ns);
+    const int nf = W.nfields;
     const unsigned tw = (unsigned)((c0 + nc - 1) / 64 - c0 / 64 + 1), sg = (unsigned)std::min(ns, 65535);
     const unsigned fg = (unsigned)((nf + 4 * SAMP_KR - 1) / (4 * SAMP_KR));
-    const size_t slot0 = (size_t)((s.kept - have + s0) % s.capacity);
-    if (layout == 1) hipLaunchKernelGGL(samples_read_rows_kernel, dim3(tw, fg, sg), dim3(256), 0, h->stream, (const double *)s.store,
-        dev_out, slot0, (size_t)s.capacity, h->ntiles, nf, ns, c0, nc);
-    else hipLaunchKernelGGL(samples_read_chains_kernel, dim3(tw, sg), dim3(256), 0, h->stream, (const double *)s.store, dev_out, slot0,
-        (size_t)s.capacity, h->ntiles, nf, ns, c0, nc);
+    if (layout == 1) hipLaunchKernelGGL(samples_read_rows_kernel, dim3(tw, fg, sg), dim3(256), 0, h->stream, W.store, dev_out, W.slot0,
+        W.cap, W.ntiles, nf, ns, c0, nc);
+    else hipLaunchKernelGGL(samples_read_chains_kernel, dim3(tw, sg), dim3(256), 0, h->stream, W.store, dev_out, W.slot0, W.cap, W.ntiles,
+        nf, ns, c0, nc);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- what the readers of the ring share
+// The readers' scratch, h->d_scratch: allocated at the first call, grows only, freed by mcmcx_destroy; every reader carves its own layout
+// out of it (tile rows, shift, tables, the host form's staging vector).  ONE for all of them is sound because every reader works on
+// h->stream alone, which is fixed at mcmcx_init: a later call's kernels run behind an earlier call's, whichever reader it was, and a host
+// form synchronises the stream before it returns, so nothing reads a staging vector after the next call may write there.
+static int samples_scratch(mcmcx_engine *h, size_t bytes)
+{
+    if (bytes <= h->scratch_cap) return 0;
+    HIPCHK(hipStreamSynchronize(h->stream));                    // an earlier call may still use the old one
+    if (h->d_scratch) (void)hipFree(h->d_scratch);
+    h->d_scratch = nullptr; h->scratch_cap = 0;
+    const hipError_t e = hipMalloc(&h->d_scratch, bytes);
+    if (e != hipSuccess) {
+        h->d_scratch = nullptr;
+        return fail(-101, "hipMalloc of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    }
+    h->scratch_cap = bytes;
+    return 0;
+}
+
+// shift[nfields] of a reduction into dshift: the caller's (host memory) or, shift == nullptr, chain 0 of window sample 0
+static int samples_shift(const SampleWin &W, const double *shift, double *dshift, hipStream_t stream)
+{
+    const int nf = W.nfields;
+    if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, stream));
+    else hipLaunchKernelGGL(diag_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, W.store, dshift, W.slot0, W.ntiles,
+        nf);
+    return 0;
+}
+
+// The T tile rows of `len` doubles in `rows` summed into row 0 (and into dst, if given) by the fixed pairwise tree of
+// moments_tree_kernel (mcx_moments.hpp has its definition), six levels per launch: the pooled moments, the summary and the covariance
+static void moments_tree_launch(hipStream_t stream, double *rows, int T, int len, double *dst)
+{
+    for (long long stride = 1;; stride *= 64) {
+        const long long groups = (T + 64 * stride - 1) / (64 * stride);
+        hipLaunchKernelGGL(moments_tree_kernel, dim3((unsigned)((len + 255) / 256), (unsigned)groups), dim3(256), 0, stream, rows, T, len,
+                           (int)stride, dst);
+        if (groups == 1) break;
+    }
+}
+
+// the host form of a result a launch left in device memory at `staged`
+static int samples_fetch(mcmcx_engine *h, void *host_out, const void *staged, size_t bytes)
+{
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, staged, bytes, hipMemcpyDeviceToHost));
     return 0;
 }

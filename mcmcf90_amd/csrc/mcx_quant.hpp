@@ -32,9 +32,7 @@ __host__ MCX_DEV unsigned long long quant_unkey(unsigned long long k) { return k
 struct QuantRanks { long long r[QUANT_MAXR]; };                 // a launch argument: staged by the launch itself
 
 struct QuantWin {
-    const double *store;                                        // [slot][ntiles][nfields][64]
-    size_t slot0, cap;                                          // ring slot of window sample 0, the ring's capacity
-    int ntiles, nfields, nchains, ns;
+    SampleWin win;                                              // the window (mcx_samples.hpp)
     int chunk;                                                  // window samples per blockIdx.z (32-bit counters stay below 2**32)
 };
 
@@ -74,16 +72,16 @@ __global__ __launch_bounds__(256) void quant_hist_kernel(QuantWin A, QuantState 
     }
     __syncthreads();
     const int nl = nlead;
-    const int w0 = (int)blockIdx.z * A.chunk, w1 = min(A.ns, w0 + A.chunk);
+    const int w0 = (int)blockIdx.z * A.chunk, w1 = min(A.win.ns, w0 + A.chunk);
     const int hs = sh + QUANT_B;                                // the prefix is the bits from hs up (none in the first pass)
-    for (size_t tile = (size_t)blockIdx.x * 4 + wave; tile < (size_t)A.ntiles; tile += (size_t)gridDim.x * 4) {
-        const bool act = tile * 64 + (size_t)lane < (size_t)A.nchains;      // the store's padding rows hold no defined values
+    for (size_t tile = (size_t)blockIdx.x * 4 + wave; tile < (size_t)A.win.ntiles; tile += (size_t)gridDim.x * 4) {
+        const bool act = tile * 64 + (size_t)lane < (size_t)A.win.nchains;      // the store's padding rows hold no defined values
         for (int j0 = w0; j0 < w1; j0 += QUANT_LB) {
             double v[QUANT_LB];
 #pragma unroll
             for (int q = 0; q < QUANT_LB; ++q)
-                v[q] = A.store[samples_row(diag_slot(A.slot0, min(j0 + q, w1 - 1), A.cap), (size_t)A.ntiles, (size_t)A.nfields, tile,
-                                           (size_t)f) + lane];
+                v[q] = A.win.store[samples_row(samples_slot(A.win.slot0, min(j0 + q, w1 - 1), A.win.cap), (size_t)A.win.ntiles,
+                                               (size_t)A.win.nfields, tile, (size_t)f) + lane];
 #pragma unroll
             for (int q = 0; q < QUANT_LB; ++q) {
                 if (j0 + q >= w1) break;                        // the whole wave
@@ -174,22 +172,22 @@ __global__ __launch_bounds__(256) void quant_counts_kernel(QuantWin A, const uns
     constexpr int LB = NQ > 8 ? 4 : QUANT_LB;                   // rows in flight: fewer where the counts take the registers
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int f = (int)blockIdx.y * 4 + wave;
-    if (f >= A.nfields) return;                                 // the whole wave
+    if (f >= A.win.nfields) return;                             // the whole wave
     unsigned long long xk[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) { xk[q] = xkey[(size_t)f * (size_t)nq + (size_t)min(q, nq - 1)]; asm volatile("" : "+v"(xk[q])); }
     unsigned int lt[NQ], le[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) { lt[q] = 0u; le[q] = 0u; }
-    const int w0 = (int)blockIdx.z * A.chunk, w1 = min(A.ns, w0 + A.chunk);
-    for (size_t tile = blockIdx.x; tile < (size_t)A.ntiles; tile += gridDim.x) {
-        const bool act = tile * 64 + (size_t)lane < (size_t)A.nchains;
+    const int w0 = (int)blockIdx.z * A.chunk, w1 = min(A.win.ns, w0 + A.chunk);
+    for (size_t tile = blockIdx.x; tile < (size_t)A.win.ntiles; tile += gridDim.x) {
+        const bool act = tile * 64 + (size_t)lane < (size_t)A.win.nchains;
         for (int j0 = w0; j0 < w1; j0 += LB) {
             double v[LB];
 #pragma unroll
             for (int u = 0; u < LB; ++u)
-                v[u] = A.store[samples_row(diag_slot(A.slot0, min(j0 + u, w1 - 1), A.cap), (size_t)A.ntiles, (size_t)A.nfields, tile,
-                                           (size_t)f) + lane];
+                v[u] = A.win.store[samples_row(samples_slot(A.win.slot0, min(j0 + u, w1 - 1), A.win.cap), (size_t)A.win.ntiles,
+                                               (size_t)A.win.nfields, tile, (size_t)f) + lane];
 #pragma unroll
             for (int u = 0; u < LB; ++u) {
                 const unsigned long long key = quant_key((unsigned long long)__double_as_longlong(v[u]));

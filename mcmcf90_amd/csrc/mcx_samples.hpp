@@ -21,6 +21,23 @@ __host__ MCX_DEV size_t samples_row(size_t slot, size_t ntiles, size_t nfields, 
     return ((slot * ntiles + tile) * nfields + field) * 64;
 }
 
+// A window of the ring as a launch argument of the store's readers (mcx_diag.hpp, mcx_quant.hpp, mcx_cov.hpp): window samples 0 .. ns - 1
+// of all chains, window sample w in ring slot samples_slot(slot0, w, cap).  The host makes it in ONE place (samples_window).  QuantWin
+// holds one; DiagArgs and CovArgs hold its members one by one (mcx_diag.hpp says why).
+struct SampleWin {
+    const double *store;                                        // [slot][ntiles][nfields][64]
+    size_t slot0, cap;                                          // ring slot of window sample 0, the ring's capacity
+    int ntiles, nfields, nchains, ns;
+};
+
+// ring slot of window sample w: (slot0 + w) % cap as in samples_read, for slot0 < cap and w < cap (a window is never longer than the ring)
+// -- without the 64-bit division the % would cost every row
+MCX_DEV size_t samples_slot(size_t slot0, int w, size_t cap)
+{
+    const size_t q = slot0 + (size_t)w;
+    return q >= cap ? q - cap : q;
+}
+
 // where field f of a tile's chains lives in the engine's state (a 64-double row)
 MCX_DEV const double *samples_src(const EngineDev &E, size_t tile, int f)
 {

@@ -411,9 +411,31 @@ class Engine:
         n = self.L.mcmcx_samples_kept(self.h, C.byref(o), C.byref(t), C.byref(f))
         return int(n), o.value, t.value, f.value
 
-    def _sample_window(self, s0, ns, c0, nc, layout):
+    def _window(self, s0, ns):
+        """(ns, oldest_iteration, thin, nfields) of a reader's window; ns = None: every retained sample from s0 on."""
         n, oldest, thin, nf = self.samples_kept()
-        ns = n - s0 if ns is None else int(ns)
+        return (n - s0 if ns is None else int(ns)), oldest, thin, nf
+
+    def _shift(self, shift, nf, who):
+        """shift as a contiguous array of nfields values, or None"""
+        if shift is None:
+            return None
+        sh = _f64(shift)
+        if sh.size != nf:
+            raise McmcError("%s: shift has %d values, a sample has %d fields" % (who, sh.size, nf))
+        return sh
+
+    def _dev(self, shape, call):
+        """A tensor on the engine's device filled by the asynchronous form `call(pointer)` of a getter, synchronised."""
+        import torch
+        t = torch.empty(shape, dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        self._chk(call(C.c_void_p(t.data_ptr())))
+        self.sync()
+        return t
+
+    def _sample_shape(self, s0, ns, c0, nc, layout):
+        """(ns, nc, iterations[ns], shape) of what samples / samples_torch return"""
+        ns, oldest, thin, nf = self._window(s0, ns)
         nc = self.nchains - c0 if nc is None else int(nc)
         its = np.array([oldest + (s0 + j) * thin for j in range(max(ns, 0))], dtype=np.int64)
         shape = (ns, nc, nf) if layout == 0 else (ns, nf, nc)
@@ -422,7 +444,7 @@ class Engine:
     def samples(self, s0=0, ns=None, c0=0, nc=None, layout=0):
         """(iterations[ns], array): retained samples s0 .. s0 + ns - 1 of chains c0 .. c0 + nc - 1 as [ns][nc][nfields] (layout 0) or
         [ns][nfields][nc] (layout 1); the fields of a chain are theta, ss per column, sspri, sigma2 per column."""
-        ns, nc, its, shape = self._sample_window(s0, ns, c0, nc, layout)
+        ns, nc, its, shape = self._sample_shape(s0, ns, c0, nc, layout)
         a = np.zeros(shape)
         if ns == 0 or nc == 0:
             return its, a
@@ -431,54 +453,34 @@ class Engine:
 
     def samples_torch(self, s0=0, ns=None, c0=0, nc=None, layout=0):
         """The same window as a float64 torch tensor on the engine's device: the copy never leaves device memory."""
-        import torch
-        ns, nc, its, shape = self._sample_window(s0, ns, c0, nc, layout)
-        t = torch.empty(shape, dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        ns, nc, its, shape = self._sample_shape(s0, ns, c0, nc, layout)
         if ns == 0 or nc == 0:
-            return its, t
-        self._chk(self.L.mcmcx_get_samples_dev(self.h, int(s0), ns, int(c0), nc, int(layout), C.c_void_p(t.data_ptr())))
-        self.sync()
-        return its, t
+            import torch
+            return its, torch.empty(shape, dtype=torch.float64, device="cuda:%d" % self.cfg.device)
+        return its, self._dev(shape, lambda p: self.L.mcmcx_get_samples_dev(self.h, int(s0), ns, int(c0), nc, int(layout), p))
 
     # --- convergence summary of the retained samples, reduced on the device (mcmcx_samples_stats)
-    def _stats_window(self, s0, ns, shift):
-        """(ns, shift as a contiguous array or None) of a summary call; ns = None: every retained sample from s0 on."""
-        n, _, _, nf = self.samples_kept()
-        ns = n - s0 if ns is None else int(ns)
-        sh = None
-        if shift is not None:
-            sh = _f64(shift)
-            if sh.size != nf:
-                raise McmcError("samples_stats: shift has %d values, a sample has %d fields" % (sh.size, nf))
-        return ns, sh
-
     def samples_stats(self, s0=0, ns=None, maxlag=16, shift=None):
         """The stats vector of retained samples s0 .. s0 + ns - 1 of all chains (include/mcmcx.h has the definition): additive over engines
         that were given the same `shift`; `samples_diag` finishes it."""
-        ns, sh = self._stats_window(s0, ns, shift)
+        ns, _, _, nf = self._window(s0, ns)
+        sh = self._shift(shift, nf, "samples_stats")
         a = np.zeros(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))))
         self._chk(self.L.mcmcx_samples_stats(self.h, int(s0), ns, int(maxlag), _dp(sh), _dp(a)))
         return a
 
     def samples_stats_torch(self, s0=0, ns=None, maxlag=16, shift=None):
         """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
-        import torch
-        ns, sh = self._stats_window(s0, ns, shift)
-        t = torch.empty(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))), dtype=torch.float64,
-                        device="cuda:%d" % self.cfg.device)
-        self._chk(self.L.mcmcx_samples_stats_dev(self.h, int(s0), ns, int(maxlag), _dp(sh), C.c_void_p(t.data_ptr())))
-        self.sync()
-        return t
+        ns, _, _, nf = self._window(s0, ns)
+        sh = self._shift(shift, nf, "samples_stats_torch")
+        return self._dev(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))),
+                         lambda p: self.L.mcmcx_samples_stats_dev(self.h, int(s0), ns, int(maxlag), _dp(sh), p))
 
     # --- exact order statistics, tail counts and quantiles of the retained samples (mcmcx_samples_order_stats)
-    def _quant_window(self, s0, ns):
-        n, _, _, nf = self.samples_kept()
-        return (n - s0 if ns is None else int(ns)), nf
-
     def samples_order_stats(self, ranks, s0=0, ns=None):
         """[nfields][nr]: the values whose keys are the ranks[k]-th smallest (0-based) among the ns x nchains values of each field in
         retained samples s0 .. s0 + ns - 1 (include/mcmcx.h has the key order: -0.0 below +0.0, NaNs at the two ends)."""
-        ns, nf = self._quant_window(s0, ns)
+        ns, _, _, nf = self._window(s0, ns)
         r = _i64(ranks).ravel()
         a = np.zeros((nf, r.size))
         self._chk(self.L.mcmcx_samples_order_stats(self.h, int(s0), ns, int(r.size), _lp(r), _dp(a)))
@@ -486,18 +488,14 @@ class Engine:
 
     def samples_order_stats_torch(self, ranks, s0=0, ns=None):
         """The same as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
-        import torch
-        ns, nf = self._quant_window(s0, ns)
+        ns, _, _, nf = self._window(s0, ns)
         r = _i64(ranks).ravel()
-        t = torch.empty((nf, r.size), dtype=torch.float64, device="cuda:%d" % self.cfg.device)
-        self._chk(self.L.mcmcx_samples_order_stats_dev(self.h, int(s0), ns, int(r.size), _lp(r), C.c_void_p(t.data_ptr())))
-        self.sync()
-        return t
+        return self._dev((nf, r.size), lambda p: self.L.mcmcx_samples_order_stats_dev(self.h, int(s0), ns, int(r.size), _lp(r), p))
 
     def samples_counts(self, x, s0=0, ns=None):
         """int64 [nfields][nq][2]: how many window values of field f have a key below (lt) and not above (le) that of x[f][q].  Exact
         and additive over engines that hold disjoint chains."""
-        ns, nf = self._quant_window(s0, ns)
+        ns, _, _, nf = self._window(s0, ns)
         xs = _f64(x)
         if xs.ndim != 2 or xs.shape[0] != nf:
             raise McmcError("samples_counts: x must be [nfields = %d][nq], got %s" % (nf, xs.shape))
@@ -508,7 +506,7 @@ class Engine:
     def samples_quantiles(self, probs, s0=0, ns=None):
         """[nfields][nq]: the quantiles at `probs` (numpy's default, linear interpolation between two order statistics) of every
         field over the window; at most QUANT_MAXR / 2 probabilities per call."""
-        ns, nf = self._quant_window(s0, ns)
+        ns, _, _, nf = self._window(s0, ns)
         p = _f64(probs).ravel()
         a = np.zeros((nf, p.size))
         self._chk(self.L.mcmcx_samples_quantiles(self.h, int(s0), ns, int(p.size), _dp(p), _dp(a)))
@@ -518,9 +516,8 @@ class Engine:
         """dict of arrays over the fields: mean, sd, rhat, ess, mcse, W, Bn, truncated; `fields` names the rows, `iterations` are the
         window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound.  With `probs` also the
         keys `probs` and `quantiles` ([nfields][nq], samples_quantiles of the same window)."""
-        _, oldest, thin, nf = self.samples_kept()
-        ns, sh = self._stats_window(s0, ns, shift)
-        table = samples_diag(self.samples_stats(s0, ns, maxlag, sh), nf, maxlag)
+        ns, oldest, thin, nf = self._window(s0, ns)
+        table = samples_diag(self.samples_stats(s0, ns, maxlag, shift), nf, maxlag)
         out = {k: table[:, j].copy() for j, k in enumerate(DIAG_COLUMNS)}
         out["fields"] = sample_field_names(self.npar, getattr(self, "nycol", 1))
         out["iterations"] = oldest + (int(s0) + np.arange(max(ns, 0), dtype=np.int64)) * thin
@@ -533,19 +530,18 @@ class Engine:
     def samples_cov_stats(self, s0=0, ns=None, shift=None):
         """The cov vector of retained samples s0 .. s0 + ns - 1 of all chains (include/mcmcx.h has the definition): additive over engines
         that were given the same `shift`; `samples_cov_finish` finishes it."""
-        ns, sh = self._stats_window(s0, ns, shift)
+        ns, _, _, nf = self._window(s0, ns)
+        sh = self._shift(shift, nf, "samples_cov_stats")
         a = np.zeros(self._chk(self.L.mcmcx_samples_cov_len(self.h)))
         self._chk(self.L.mcmcx_samples_cov(self.h, int(s0), ns, _dp(sh), _dp(a)))
         return a
 
     def samples_cov_stats_torch(self, s0=0, ns=None, shift=None):
         """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
-        import torch
-        ns, sh = self._stats_window(s0, ns, shift)
-        t = torch.empty(self._chk(self.L.mcmcx_samples_cov_len(self.h)), dtype=torch.float64, device="cuda:%d" % self.cfg.device)
-        self._chk(self.L.mcmcx_samples_cov_dev(self.h, int(s0), ns, _dp(sh), C.c_void_p(t.data_ptr())))
-        self.sync()
-        return t
+        ns, _, _, nf = self._window(s0, ns)
+        sh = self._shift(shift, nf, "samples_cov_stats_torch")
+        return self._dev(self._chk(self.L.mcmcx_samples_cov_len(self.h)),
+                         lambda p: self.L.mcmcx_samples_cov_dev(self.h, int(s0), ns, _dp(sh), p))
 
     def samples_cov(self, s0=0, ns=None, shift=None, fields="theta"):
         """dict: `mean`, `cov`, `corr` of the window over all chains, `n` = ns x nchains, `fields` the names of the rows.  fields="theta"

@@ -319,3 +319,46 @@ def test_covariance_of_a_gaussian_target_and_the_next_run():
     e2.init()
     assert e2.run() == 0
     e2.close()
+
+
+def test_readers_share_one_scratch_back_to_back():
+    """The summary, the order statistics and counts and the covariance carve their work areas out of ONE grow-only scratch of the engine.
+    The asynchronous forms are issued back to back with nothing synchronised in between -- counts with one threshold (the smallest scratch),
+    stats at maxlag 0, cov, order statistics at 32 ranks (a regrow while the earlier calls are still queued), stats at maxlag 3 -- each into
+    a tensor of its own; after ONE sync every tensor holds the bits of the host form of the same call made alone on a second engine with
+    the same seed.  70 chains (two tiles, the second ragged), npar 3, a ring of 8 under 20 kept iterations (wrapped)."""
+    import torch
+    from mcmcf90_amd import engine_from_problem
+
+    def eng():
+        e = engine_from_problem(dict(nsimu=20, adaptint=7, updatesigma=1), _gauss(3, 31, sigma2=0.6, nobs=11), nchains=70, chain_id0=4)
+        e.set_samples(1, 1, 8)
+        e.init()
+        assert e.run() == 0 and e.samples_kept()[:2] == (8, 13)
+        return e
+
+    a, b = eng(), eng()
+    nf = a.samples_kept()[3]
+    assert nf == 6
+    x = np.full((nf, 1), 0.05)
+    ranks = np.linspace(0, 8 * 70 - 1, 32).astype(np.int64)
+    L, h = a.L, a.h
+
+    def dev(*shape, dtype=torch.float64):
+        return torch.empty(shape, dtype=dtype, device="cuda:%d" % a.cfg.device)
+    # every tensor first: an allocation between two calls may synchronise the device
+    t_cnt, t_s0, t_cov = dev(nf, 1, 2, dtype=torch.int64), dev(L.mcmcx_samples_stats_len(h, 0)), dev(L.mcmcx_samples_cov_len(h))
+    t_os, t_s3 = dev(nf, 32), dev(L.mcmcx_samples_stats_len(h, 3))
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    assert L.mcmcx_samples_counts_dev(h, 0, 8, 1, _dp(x), ptr(t_cnt)) == 0
+    assert L.mcmcx_samples_stats_dev(h, 0, 8, 0, None, ptr(t_s0)) == 0
+    assert L.mcmcx_samples_cov_dev(h, 0, 8, None, ptr(t_cov)) == 0
+    assert L.mcmcx_samples_order_stats_dev(h, 0, 8, 32, ranks.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t_os)) == 0
+    assert L.mcmcx_samples_stats_dev(h, 0, 8, 3, None, ptr(t_s3)) == 0
+    a.sync()
+    assert np.array_equal(t_cnt.cpu().numpy(), b.samples_counts(x, 0, 8)), "counts"
+    _same(t_s0.cpu().numpy(), b.samples_stats(0, 8, 0), "stats, maxlag 0")
+    _same(t_cov.cpu().numpy(), b.samples_cov_stats(0, 8), "cov")
+    _same(t_os.cpu().numpy().ravel(), b.samples_order_stats(ranks, 0, 8).ravel(), "order statistics")
+    _same(t_s3.cpu().numpy(), b.samples_stats(0, 8, 3), "stats, maxlag 3")
+    a.close(); b.close()
