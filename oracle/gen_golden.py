@@ -181,6 +181,70 @@ def long_cases():
     return c
 
 
+EDGE_OUT = os.path.join(OUT, "edge")      # kept out of golden_util.names(): whole chains, compared by tests/test_oracle_edge_golden.py
+
+
+def edge_cases():
+    """name -> (cfg kwargs, Problem kwargs, chain_id): the problems of tests/edge_problems.py (sums of squares that are +inf, NaN or
+    subnormal, an infinite sigma2), one chain of 170 iterations each, the chains the GPU tests start from (chain_id0 = 6).  The fixtures hold
+    the WHOLE of chain.mat, sschain.mat and s2chain.mat next to rng_n, chaincmat and chainmean.
+    method = 'ram': the reference STOPS at the first NaN alpha (a = NaN fails `a >= 0`, MCMC_run_ram.F90:166-171, the downdate's norm test
+    fails on NaN, dchdd.f:150-153, and choldowndate without its info argument stops, matutils.F90:719-722) before it writes a chain: the
+    fixture then holds stop_at = the smallest nsimu at which the reference stops, found by bisection over the reference alone, and the
+    chain of the run with nsimu = stop_at - 1 (cfg_nsimu is that run's).
+    A subnormal mcmcsigma2.dat is read exactly: the x8 .. x10 chains equal the unit-scale chain's run lengths and stream position."""
+    sys.path.insert(0, os.path.join(os.path.dirname(OUT)))
+    import edge_problems as ep
+    am = dict(nsimu=170, adaptint=50, updatesigma=0)
+    pri = lambda d: dict(pri_mu=np.full(d, 0.1), pri_sig=np.where(np.arange(d) % 3 == 1, -1.0, 1.0))
+    sym = lambda p: dict(p, cmat0=0.5 * (p["cmat0"] + p["cmat0"].T))        # (the pinned dgesvd is defined for a symmetric matrix)
+    c = {}
+    c["x1_ovf7_am"] = (am, ep.overflow_ar1(7, 10.0, 0.3), 6)
+    c["x2_ovf13_dr"] = (dict(am, drscale=3.0), ep.overflow(13, 16.0, 0.3), 6)
+    c["x3_ovf20_ram"] = (dict(am, method="ram"), ep.overflow(20, 25.0, 0.3), 6)
+    c["x4_ovf12_scam"] = (dict(am, method="scam"), sym(ep.overflow(12, 15.0, 0.5)), 6)
+    c["x5_ovf9_er"] = (dict(am, method="er"), ep.overflow(9, 11.0, 0.3), 6)
+    # (chain 14: seven accepted NaN proposals, five accepted +inf ones behind them and six rejections on the prior alone; chain 6 meets no NaN)
+    c["x6_ovf9_er_priors"] = (dict(am, method="er"), dict(ep.overflow(9, 11.0, 0.3), **pri(9)), 14)
+    c["x7_ovf10_s2inf"] = (dict(am, **ep.INF_SIGMA2), dict(ep.overflow_ar1(10, 10.0, 0.3), nobs=1), 6)
+    c["x8_sub20_am"] = (am, ep.subnormal(20, 2.0 ** -1030), 6)
+    c["x9_sub20_ram"] = (dict(am, method="ram"), ep.subnormal(20, 2.0 ** -1030), 6)
+    c["x10_sub20_am_1060"] = (am, ep.subnormal(20, 2.0 ** -1060), 6)
+    return c
+
+
+def main_edge(only):
+    os.makedirs(EDGE_OUT, exist_ok=True)
+    for name, (ckw, pkw, chain_id) in edge_cases().items():
+        if only and name not in only:
+            continue
+        cfg = po.make_cfg(**ckw)
+        prob = po.Problem(**pkw)
+        out = {"chain_id": chain_id, "stop_at": 0}
+        run = lambda n: rr.run_reference(po.make_cfg(**dict(ckw, nsimu=n)), prob, chain_id=chain_id, pinned_svd=bool(cfg.usesvd), allow_stop=True)
+        r = run(cfg.nsimu)
+        if r.stopped:
+            lo, hi = 2, cfg.nsimu                               # runs of lo iterations end, runs of hi stop
+            assert not run(lo).stopped
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (lo, mid) if run(mid).stopped else (mid, hi)
+            out["stop_at"] = hi
+            cfg = po.make_cfg(**dict(ckw, nsimu=lo))
+            r = run(lo)
+        assert not r.stopped and int(r.chain[:, -1].sum()) == cfg.nsimu
+        out.update(rng_n=r.rng_n, chain=r.chain, sschain=r.sschain, chaincmat=r.chaincmat, chainmean=r.chainmean)
+        if cfg.updatesigma:
+            out["s2chain"] = r.s2chain
+        for f, _ in po.Cfg._fields_:
+            out["cfg_" + f] = getattr(cfg, f)
+        for kk, v in pkw.items():
+            out["prob_" + kk] = np.asarray(v)
+        path = os.path.join(EDGE_OUT, name + ".npz")
+        np.savez_compressed(path, **out)
+        print("%-28s nsimu=%d stop_at=%d rng_n=%d  %d bytes" % (name, cfg.nsimu, out["stop_at"], r.rng_n, os.path.getsize(path)))
+
+
 def state_at(chain, its):
     """Rows of chain.mat (theta..., repeat count) -> the state after iterations `its` (1 = the start point, MCMC_aux.F90:167-175).
     tests/golden_util.py's state_at applies the same rule to the oracle's and the device's rows: keep the two alike."""
@@ -249,6 +313,7 @@ def main():
             out["prob_" + kk] = np.asarray(v)
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
         print("%-28s chainind=%d rng_n=%d" % (name, r.chainind, r.rng_n))
+    main_edge(only)
     main_long(only)
 
 

@@ -472,6 +472,16 @@ static void updatesigma2(mcxo_chain *c, const double *ss)
     }
 }
 
+/* test bookkeeping, no part of the reference: an evaluated proposal (first stage, second stage, a SCAM component) whose sum of
+ * squares is NaN in some column, or else +inf in some column (the regime of tests/edge_problems.py; MCMC_run_er computes no alpha
+ * to tell it from) */
+static void count_ss(mcxo_chain *c, const double *ss)
+{
+    int nan = 0, inf = 0;
+    for (int j = 0; j < c->ny; ++j) { if (ss[j] != ss[j]) nan = 1; else if (ss[j] > DBL_MAX) inf = 1; }
+    if (nan) c->n_ss_nan++; else if (inf) c->n_ss_inf++;
+}
+
 /* MCMC_propose, MCMC_DRAM.F90:20-31 (usesvd == 0): newpar = oldpar + R'z; z kept for RAM */
 static void propose(mcxo_chain *c, const double *oldpar, const double *R, double *newpar, double *zout)
 {
@@ -812,7 +822,7 @@ int mcxo_chain_run(mcxo_chain *c, int upto)
                 inb = mcxo_checkbounds(&c->tgt, newpar);
                 if (!inb) { if (!g->dodr) c->bndstayed++; c->alpha12 = 0.0; reject = 1; }
                 else {
-                    pri2 = mcxo_priorfun(&c->tgt, newpar); mcxo_ssfun_cols(&c->tgt, newpar, ss2v);
+                    pri2 = mcxo_priorfun(&c->tgt, newpar); mcxo_ssfun_cols(&c->tgt, newpar, ss2v); count_ss(c, ss2v);
                     c->alpha12 = alpha_cols(c, c->ss1v, c->sspri1, ss2v, pri2);
                     reject = mcmc_reject(c, c->alpha12);
                 }
@@ -842,7 +852,7 @@ int mcxo_chain_run(mcxo_chain *c, int upto)
                 if (pri2 >= sscrit) { reject = 1; c->erstayed++; }
                 else {
                     sscrit = c->sigma2v[0] * (sscrit - pri2);       /* MCMC_run_er.F90:72 "problem here if nycol > 1" */
-                    mcxo_ssfun_cols(&c->tgt, newpar, ss2v);          /* default ssfunction_er: no early exit */
+                    mcxo_ssfun_cols(&c->tgt, newpar, ss2v); count_ss(c, ss2v);          /* default ssfunction_er: no early exit */
                     double s2 = 0.0;                                 /* sum(ss2) */
                     for (int j_ = 0; j_ < ny; ++j_) s2 = s2 + ss2v[j_];
                     reject = (s2 >= sscrit) ? 1 : 0;
@@ -864,7 +874,7 @@ int mcxo_chain_run(mcxo_chain *c, int upto)
             inb = mcxo_checkbounds(&c->tgt, newpar);
             if (!inb) { c->bndstayed++; reject = 1; }              /* alpha12 left stale: MCMC_run_ram.F90:52-54 */
             else {
-                pri2 = mcxo_priorfun(&c->tgt, newpar); mcxo_ssfun_cols(&c->tgt, newpar, ss2v);
+                pri2 = mcxo_priorfun(&c->tgt, newpar); mcxo_ssfun_cols(&c->tgt, newpar, ss2v); count_ss(c, ss2v);
                 c->alpha12 = alpha_cols(c, c->ss1v, c->sspri1, ss2v, pri2);
                 reject = mcmc_reject(c, c->alpha12);
             }
@@ -877,7 +887,7 @@ int mcxo_chain_run(mcxo_chain *c, int upto)
                 for (int j_ = 0; j_ < ny; ++j_) ss2v[j_] = DBL_MAX;
                 pri2 = DBL_MAX; c->alpha12 = 0.0; reject = 1;
             } else {
-                pri2 = mcxo_priorfun(&c->tgt, newpar); mcxo_ssfun_cols(&c->tgt, newpar, ss2v);
+                pri2 = mcxo_priorfun(&c->tgt, newpar); mcxo_ssfun_cols(&c->tgt, newpar, ss2v); count_ss(c, ss2v);
                 c->alpha12 = alpha_cols(c, c->ss1v, c->sspri1, ss2v, pri2);
                 reject = mcmc_reject(c, c->alpha12);
             }
@@ -888,7 +898,7 @@ int mcxo_chain_run(mcxo_chain *c, int upto)
                 inb = mcxo_checkbounds(&c->tgt, newpar2);
                 if (!inb) { c->bndstayed++; reject = 1; }
                 else {
-                    pri3 = mcxo_priorfun(&c->tgt, newpar2); mcxo_ssfun_cols(&c->tgt, newpar2, ss3v);
+                    pri3 = mcxo_priorfun(&c->tgt, newpar2); mcxo_ssfun_cols(&c->tgt, newpar2, ss3v); count_ss(c, ss3v);
                     double a13 = dr_alpha13(c, c->oldpar, c->ss1v, c->sspri1, newpar, ss2v, pri2, c->alpha12, newpar2, ss3v, pri3);
                     reject = mcmc_reject(c, a13);
                     if (!reject) { c->draccepted++; memcpy(newpar, newpar2, sizeof(double) * n); for (int j_ = 0; j_ < ny; ++j_) ss2v[j_] = ss3v[j_]; pri2 = pri3; }

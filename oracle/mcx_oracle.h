@@ -98,6 +98,9 @@ typedef struct mcxo_chain {
     /* bookkeeping for tests that replace the factors of an adaptation from outside (tests/test_oracle_fuzz_reference.py):
      * calls of MCMC_calculate_R so far, and whether the latest covtor_svd floored its singular values (info = -1) */
     int n_calcR, svd_floored;
+    /* evaluated proposals (both stages, every SCAM component) whose sum of squares was +inf / NaN: the regime of the tests at
+     * overflowing targets (tests/edge_problems.py), which early rejection shows nowhere else */
+    int n_ss_inf, n_ss_nan;
 } mcxo_chain;
 
 mcxo_chain *mcxo_chain_create(const mcxo_cfg *cfg, const mcxo_target *tgt, const double *par0,

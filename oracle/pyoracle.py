@@ -55,7 +55,8 @@ class Chain(C.Structure):
                 ("oldpar", _DP), ("ss1", C.c_double), ("sspri1", C.c_double), ("alpha12", C.c_double),
                 ("continue_on_downdate_fail", C.c_int), ("qcovstd", _DP), ("erstayed", C.c_int),
                 ("ny", C.c_int), ("ss1v", C.c_double * 32), ("sigma2v", C.c_double * 32), ("nobsv", C.c_int * 32),       # MCXO_NYMAX
-                ("trmv_desc", C.c_int), ("last_u", _DP), ("n_calcR", C.c_int), ("svd_floored", C.c_int)]
+                ("trmv_desc", C.c_int), ("last_u", _DP), ("n_calcR", C.c_int), ("svd_floored", C.c_int),
+                ("n_ss_inf", C.c_int), ("n_ss_nan", C.c_int)]
 
 
 _lib = None
@@ -211,6 +212,7 @@ def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_dow
         r.stayed, r.bndstayed, r.draccepted, r.drtries = c.stayed, c.bndstayed, c.draccepted, c.drtries
         r.nprop = c.nprop
         r.erstayed = c.erstayed
+        r.n_ss_inf, r.n_ss_nan = c.n_ss_inf, c.n_ss_nan      # evaluated proposals with ss = +inf / NaN (all stages, all SCAM components)
         r.rng_n = c.rng.n
         r.rng_saved, r.rng_saved_y = c.rng.saved, c.rng.saved_y
         r.ram_downdate_fail = c.ram_downdate_fail

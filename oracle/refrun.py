@@ -132,7 +132,7 @@ def read_svd_log(path):
     return calls
 
 
-def run_reference(cfg, prob, seed=0x6D636D63, chain_id=0, keep=False, timeout=600, pinned_svd=False, timing_only=False, svd_log=False):
+def run_reference(cfg, prob, seed=0x6D636D63, chain_id=0, keep=False, timeout=600, pinned_svd=False, timing_only=False, svd_log=False, allow_stop=False):
     """timing_only: run in a tmpfs scratch directory when there is one, time the reference process alone (r.seconds)
     and do not parse its output files (bench.py's cpu_baseline leg)."""
     if not available():
@@ -156,7 +156,12 @@ def run_reference(cfg, prob, seed=0x6D636D63, chain_id=0, keep=False, timeout=60
         r.scratch = "tmpfs" if shm else "disk"
         r.stdout = p.stdout.decode(errors="replace")
         r.returncode = p.returncode
+        r.stopped = False
         if not os.path.exists(os.path.join(d, "chain.mat")):
+            if allow_stop and os.path.exists(os.path.join(d, "rng.log")):   # the reference stopped mid-run: only the stream position is left
+                r.stopped = True
+                r.rng_n = int(open(os.path.join(d, "rng.log")).read().split()[-1])
+                return r
             raise RuntimeError("reference run produced no chain:\n" + r.stdout[-2000:])
         if timing_only:
             return r

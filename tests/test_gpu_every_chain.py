@@ -21,6 +21,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import edge_problems as ep
+
 pytestmark = pytest.mark.gpu
 
 NCH, CHAIN_ID0 = 583, 6
@@ -40,7 +42,7 @@ def P(kind, d, **opt):
 
 def _bounded(prob):
     opt = dict(prob[2])
-    return prob[0] == "gauss" and bool(opt.get("bounded", prob[1] in BOUNDED and not opt.get("drscale")))
+    return prob[0] == "gauss" and "edge" not in opt and bool(opt.get("bounded", prob[1] in BOUNDED and not opt.get("drscale")))
 
 
 def _bits(a):
@@ -71,6 +73,15 @@ def _problem(prob):
     A = r.standard_normal((d, d)) / np.sqrt(d)
     lam = A @ A.T + np.eye(d)
     pkw = dict(kind="gauss", npar=d, par0=np.full(d, 0.1), cmat0=np.linalg.inv(lam), mu=np.linspace(-0.5, 0.5, d), lam=lam)
+    if "edge" in opt:                                           # tests/edge_problems.py: "ovf:T:c" (the pair block), "ar1:T:c", "s2:T:c", "sub:e" (t = 2**-e)
+        how, *arg = opt["edge"].split(":")
+        if how == "sub":
+            pkw = ep.subnormal(d, 2.0 ** -int(arg[0]))
+        else:
+            pkw = (ep.overflow if how == "ovf" else ep.overflow_ar1)(d, float(arg[0]), float(arg[1]))
+        if how == "s2":
+            ckw.update(ep.INF_SIGMA2)
+            pkw.update(nobs=1)
     if _bounded(prob):
         # (with delayed rejection only the SECOND stage's exits are counted, MCMC_run.F90:49, and its proposals are a third as long: +-1.5)
         b = 1.5 if ckw["drscale"] else 2.5
@@ -129,6 +140,8 @@ def _oracle_all(oracle, prob):
         o = dict(theta=np.array([r.theta for r in rs]), acc=np.array([r.accepted for r in rs], dtype=np.uint8),
                  scal=np.array([[r.ss1, r.sspri1, r.sigma2, r.alpha12] for r in rs]), rng=np.array([r.rng_n for r in rs], dtype=np.uint64),
                  ctr=np.array([[r.stayed, r.bndstayed, r.drtries, r.draccepted, r.erstayed] for r in rs], dtype=np.int64),
+                 nprop=np.array([r.nprop for r in rs], dtype=np.int64), ssinf=np.array([r.n_ss_inf for r in rs], dtype=np.int64),
+                 ssnan=np.array([r.n_ss_nan for r in rs], dtype=np.int64),
                  R=np.array([r.R for r in rs]), qstd=np.array([r.qcovstd for r in rs]), R2=np.array([r.R2 for r in rs]), iC=np.array([r.iC for r in rs]),
                  cmat=np.array([r.chaincmat for r in rs]), mean=np.array([r.chainmean for r in rs]), wsum=np.array([r.chainwsum for r in rs]),
                  alpha=np.array([r.alpha for r in rs]), ss1v=np.array([r.ss1v for r in rs]), s2chain=np.array([r.s2chain for r in rs]).reshape(nch, nsimu, -1))
@@ -149,6 +162,36 @@ def _regime(prob, o):
     # the first stage's rate: with delayed rejection a first-stage rejection is a second-stage try
     rate1 = 1.0 - drtries.sum() / (nch * (nsimu - 1.0)) if ckw["drscale"] else rate
     below_one = "sigma2" in opt and sum(opt["sigma2"]) < 2
+    if "edge" in opt:
+        # no NaN and no infinity in a state, factor or covariance: the reference's fixtures (tests/golden/edge/) show none
+        for k in ("theta", "R", "R2", "iC", "qstd", "cmat", "mean", "wsum"):
+            assert np.isfinite(o[k]).all(), k
+        tiles = [slice(t, t + 64) for t in range(0, nch - 63, 64)]
+        scam = ckw["method"] == "scam"
+        if opt["edge"].startswith("sub"):
+            ss1 = o["scal"][:, 0]
+            assert ep.is_subnormal(ss1).all() and len(np.unique(ss1)) == nch, (ss1.min(), ss1.max(), len(np.unique(ss1)))
+            if scam:                                            # (an iteration of SCAM nearly always moves: the last component's alpha, as below)
+                a = np.minimum(o["alpha"][:, 1:], 1.0).mean()
+                assert rate > 0.9 and 0.5 < a < 0.9, (rate, a)
+            else:
+                assert 0.1 < rate1 < 0.5, rate1
+            return
+        ninf, nnan, nprop = o["ssinf"].sum(), o["ssnan"].sum(), float(o["nprop"].sum())
+        print("%s: first-stage rate %.3f, ss = +inf %.4f, NaN %.4f of %d proposals" % (prob, rate1, ninf / nprop, nnan / nprop, nprop))
+        assert all(o["ssnan"][t].any() for t in tiles) and all(o["ssinf"][t].any() for t in tiles)      # every full tile holds both
+        if scam:
+            assert ninf > 0 and nnan > 0
+        else:
+            assert 0.1 < rate1 < 0.75, rate1
+            assert ninf >= 0.01 * nprop and nnan >= 0.005 * nprop, (ninf / nprop, nnan / nprop)
+        if ckw["updatesigma"]:                                  # the gamma draw overflowed in part of the chains, not in all
+            s2 = o["s2chain"][:, 1:, 0]
+            print("sigma2 = +inf in %.3f of the draws" % np.isinf(s2).mean())
+            assert not np.isnan(s2).any() and 0.05 < np.isinf(s2).mean() < 0.95 and all(np.isinf(s2[t]).any() and np.isfinite(s2[t]).any() for t in tiles)
+        if ckw["drscale"]:
+            assert dracc.sum() > nch and (drtries - dracc).sum() > nch
+        return
     if ckw["method"] == "scam":
         # an iteration is npar one-dimensional steps and `accepted` says that one of them moved, which every iteration does.  The oracle's
         # alpha trace holds the LAST component's alpha of each iteration: a step as long as the target's own standard deviation along its
@@ -249,6 +292,28 @@ def _cases():
         add("scam%d" % nw, G(12, method="scam", nsimu=120), k, dict(MCMCX_SCAM_WAVES=str(nw)))
     # ---- two response columns in one launch
     add("cols", P("cols", 3), "step_kernel_cols"); add("cols", P("cols", 3, method="scam"), "step_kernel_cols<scam>")
+    # ---- sums of squares that are +inf, NaN or subnormal (tests/edge_problems.py; T and c of every overflow problem chosen on the CPU so that the
+    # oracle alone meets _regime's conditions).  The Metropolis decision is restated in every form: a NaN alpha draws no uniform and rejects
+    # (MCMC_DRAM.F90:140-155), early rejection accepts a NaN proposal (MCMC_run_er.F90:72-78: the comparison is false)
+    SUB = "sub:1030"
+    lds0 = dict(MCMCX_LDS_SCRATCH="0")
+    for e7, e50, e20 in (("ar1:10:0.3", "ovf:60:0.15", "ovf:25:0.3"), (SUB, SUB, SUB)):
+        add("lane", G(7, edge=e7), LDSR, LANE); add("lane", G(50, edge=e50), LDSV, LANE); add("lane", G(20, edge=e20), AM, LANE, lds0)
+        add("group", G(20, edge=e20), "group_step_kernel", GRP)
+    for e in ("ovf:16:0.3", SUB):
+        add("lane", G(13, drscale=3.0, edge=e), "step_kernel_dr", LANE, dict(MCMCX_DR_BIG="0"))
+        add("quad", G(13, drscale=3.0, edge=e), "group_step_kernel<quad, DR>", QUAD)
+    add("lane_big", G(13, drscale=3.0, edge="ovf:16:0.3"), "step_kernel_dr_big", LANE, dict(MCMCX_DR_BIG="1"))
+    for e17, e24, e10 in (("ovf:21:0.3", "ovf:30:0.3", "ovf:12:0.3"), (SUB, SUB, SUB)):
+        add("group", G(17, drscale=3.0, edge=e17), "group_step_kernel<DR>", GRP); add("group", G(24, drscale=2.0, edge=e24), "group_step_kernel<DR2>", GRP)
+        add("quad", G(10, edge=e10), "group_step_kernel<quad>", QUAD)
+    xer9, xer20 = G(9, method="er", priors=1, edge="ovf:11:0.3"), G(20, method="er", edge="ovf:25:0.3")
+    add("lane", xer9, LDSR, LANE); add("quad", xer9, "group_step_kernel<quad>", QUAD); add("group", xer20, "group_step_kernel", GRP)
+    xs10 = G(10, edge="s2:10:0.3")                              # sigma2 = +inf in a third of the gamma draws: (ss2 - ss1) / inf is 0 or NaN
+    add("lane", xs10, LDSR, LANE); add("group", xs10, "group_step_kernel", GRP); add("quad", xs10, "group_step_kernel<quad>", QUAD)
+    for e in ("ovf:15:0.5", SUB):
+        xsc = G(12, method="scam", nsimu=120, edge=e)
+        add("scam1", xsc, "scam_kernel", dict(MCMCX_SCAM_WAVES="1")); add("scam4", xsc, "scam_mw_kernel<4>", dict(MCMCX_SCAM_WAVES="4"))
     return C
 
 
@@ -290,10 +355,11 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     tri = (lambda a: a) if full else (lambda a: np.triu(a))
     failures = []
 
-    def check(name, got, want):
+    def check(name, got, want, nan_ok=False):
+        # nan_ok: a NaN equals a NaN whatever its sign and payload (x86 and gfx950 generate different default NaNs).  Everything else bit for bit
         got, want = np.asarray(got), np.asarray(want)
         assert got.shape == want.shape, (name, got.shape, want.shape)
-        eq = (_bits(got) == _bits(want)) if got.dtype.kind == "f" else (got == want)
+        eq = ep.same_bits_or_nan(got, want) if nan_ok else (_bits(got) == _bits(want)) if got.dtype.kind == "f" else (got == want)
         bad = np.flatnonzero(~eq.reshape(nch, -1).all(axis=1))
         if len(bad):
             failures.append("%s: %d chains, the first: %s" % (name, len(bad), bad[:12]))
@@ -302,7 +368,8 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     check("theta", theta, o["theta"])
     for j, name in enumerate(("ss1", "sspri1", "sigma2", "alpha12")):
         if name != "alpha12" or ckw["method"] != "er":          # (MCMC_run_er computes no alpha)
-            check(name, scal[:, j], o["scal"][:, j])
+            # (a NaN only where one can legitimately be, in the edge cases: alpha12, and ss1 under early rejection, which accepts a NaN proposal)
+            check(name, scal[:, j], o["scal"][:, j], nan_ok="edge" in dict(prob[2]) and (name == "alpha12" or (name == "ss1" and ckw["method"] == "er")))
     check("stream position", rng, o["rng"])
     for j, name in enumerate(("stayed", "bndstayed", "drtries", "draccepted", "erstayed")):
         check(name, ctr[:, j], o["ctr"][:, j])

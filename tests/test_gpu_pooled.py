@@ -872,8 +872,11 @@ def test_pooled_mode_with_response_columns(oracle, name, extra):
     e.close()
 
 
-def _restate_pooled_ram(oracle, ckw, pkw, N):
-    """pooled_ram_tick, tick by tick, on N single-chain oracles that never adapt on their own: returns (chains, final factor, initial state, floor hits)."""
+def _restate_pooled_ram(oracle, ckw, pkw, N, log=None):
+    """pooled_ram_tick, tick by tick, on N single-chain oracles that never adapt on their own: returns (chains, final factor, initial state, floor hits).
+    log, if given, collects (iteration, chains whose alpha was NaN, whether the factor was replaced) of every tick.
+    A statistic that is not finite (one chain's NaN alpha is enough) is refused, as pooled_reduce refuses it (error -46): the restatement ends
+    at that tick, the chains standing on its iteration, and only a caller that reads the log may meet it."""
     d, condmax = int(pkw["npar"]), float(ckw.get("condmax", 0.0))
     nsimu, adaptint, nu, target = int(ckw["nsimu"]), int(ckw["adaptint"]), float(ckw["nuparam"]), float(ckw["alphatarget"])
     plain = oracle.make_cfg(**dict(ckw, doadapt=0, method="dram"))
@@ -919,6 +922,10 @@ def _restate_pooled_ram(oracle, ckw, pkw, N):
             a = rs * (ch.alpha12 - target)
             X[c] = [u[k] / su * a for k in range(d)]
             sgn[c] = 1.0 if a >= 0.0 else -1.0
+        if not np.isfinite(X).all():
+            assert log is not None, "pooled RAM refuses the tick of iteration %d: a non-finite statistic" % it
+            log.append((it, sum(math.isnan(ch.alpha12) for ch in chains), False))
+            return chains, R, st, floored
         cnt = tree_over_chains(np.ones(N))
         S = np.zeros((d, d))
         for j in range(d):
@@ -936,8 +943,11 @@ def _restate_pooled_ram(oracle, ckw, pkw, N):
             R = svd_factor(S, False)
         else:
             Af = np.asfortranarray(S.copy())
-            if oracle.lib().mcxo_potrf_u(d, Af.ctypes.data_as(C.POINTER(C.c_double))) == 0:
+            ok = oracle.lib().mcxo_potrf_u(d, Af.ctypes.data_as(C.POINTER(C.c_double))) == 0
+            if ok:
                 R = np.triu(np.array(Af))
+            if log is not None:
+                log.append((it, sum(math.isnan(ch.alpha12) for ch in chains), ok))
         for ch in chains:
             ch.set_R(R)
     for ch in chains:
@@ -1177,3 +1187,161 @@ def test_pooled_am_with_svd_factor_matches_restatement(oracle, mfma, condmax, bu
     for ch in chains:
         ch.close()
     e.close()
+
+
+# ---------------------------------------------------------------- sums of squares that are +inf, NaN or subnormal (tests/edge_problems.py)
+def _edge_case(name):
+    """(cfg keywords, problem keywords, chains, environment, kernel) of a pooled case on an overflowing ("ovf") or subnormal ("sub") Gaussian target.
+    T and c of every overflow problem were chosen on the CPU so that the restatement's oracle chains alone meet _edge_regime's conditions.
+    Chain counts and run lengths are those of the tests above for the same kernels."""
+    import edge_problems as ep
+    form, how = name.rsplit("_", 1)
+    d, T, c = {"am24": (24, 30.0, 0.3), "am50": (50, 60.0, 0.15), "dr24": (24, 30.0, 0.3), "ram50ks": (50, 45.0, 0.15), "ram50w2": (50, 45.0, 0.15),
+               "scam30": (30, 37.0, 0.5)}[form]
+    pkw = ep.overflow(d, T, c, blk={"am50": 0.8, "ram50ks": 0.6, "ram50w2": 0.6}.get(form, 0.5)) if how == "ovf" else ep.subnormal(d, 2.0 ** -1030)
+    env = dict(MCMCX_POOLED_WAVES="1", MCMCX_POOLED_KS="0")
+    if form.startswith("ram"):
+        ckw = dict(nsimu=130, method="ram", adaptint=20, updatesigma=0, nuparam=0.7, alphatarget=0.234, condmax=0.0)
+        env = dict(MCMCX_POOLED_WAVES="2", MCMCX_POOLED_KS="1" if form.endswith("ks") else "0")
+        return ckw, pkw, 200, env, "pooled_mfma_ks_kernel" if form.endswith("ks") else "pooled_mfma_kernel<false, true>"
+    if form.startswith("scam"):
+        pkw["cmat0"] = 0.5 * (pkw["cmat0"] + pkw["cmat0"].T)     # (the pinned dgesvd is defined for a symmetric matrix)
+        return dict(nsimu=60, adaptint=25, updatesigma=0, method="scam"), pkw, 70, env, "scam_pooled_kernel"
+    ckw = dict(nsimu=230, adaptint=100, updatesigma=0)
+    if form.startswith("dr"):
+        ckw["drscale"] = 2.0
+        env["MCMCX_POOLED_MFMA_DR_MIN"] = "1"
+        return ckw, pkw, 70, env, "pooled_mfma_kernel<true>"
+    return ckw, pkw, 130, env, "pooled_mfma_kernel<false>"
+
+
+def _edge_restate(oracle, name):
+    """The restatement of a case: (chains, what the shared factor must be: {getter index or name: array}, the RAM tick log)"""
+    ckw, pkw, N, _, _ = _edge_case(name)
+    d = int(pkw["npar"])
+    if ckw.get("method") == "ram":
+        log = []
+        chains, R, st, _ = _restate_pooled_ram(oracle, ckw, pkw, N, log=log)
+        if not log[-1][2]:                                      # refused at the tick of iteration k: the run up to k - 1 is what there is to compare
+            for ch in chains:
+                ch.close()
+            chains, R, st, _ = _restate_pooled_ram(oracle, dict(ckw, nsimu=log[-1][0] - 1), pkw, N)
+        assert not np.array_equal(R, st["R"])                   # the factor did adapt
+        return chains, {"R": np.triu(R)}, log
+    if ckw.get("method") == "scam":
+        cfg = oracle.make_cfg(**dict(ckw, doadapt=0))
+        prob = oracle.Problem(**pkw)
+        chains = [oracle.LiveChain(cfg, prob, chain_id=c) for c in range(N)]
+        state, tick, nsimu = {}, ckw["adaptint"], ckw["nsimu"]
+        par0, cmat0 = np.asarray(pkw["par0"], float), np.asarray(pkw["cmat0"], float)
+        for t in list(range(tick, nsimu, tick)) + [nsimu]:
+            for ch in chains:
+                ch.run(t)
+            if t < nsimu:
+                theta = np.array([ch.theta for ch in chains])
+                cnt, s1, s2 = _pooled_moments(theta, par0, N)
+                state = _merge_and_factor(oracle, state, cnt, s1, s2, par0, d, t == tick, cmat0, 0)
+                state = _scam_factor(oracle, state, d, cfg.condmax)
+                for ch in chains:
+                    ch.set_R(state["U"]); ch.set_qcovstd(state["std"])
+        return chains, {"U": state["U"], "std": state["std"]}, None
+    chains, st, log = _restate_pooled(oracle, ckw, pkw, N)
+    assert log
+    want = {"R": np.triu(st["R"])}
+    if ckw.get("drscale", 0.0) > 0.0:
+        want.update(R2=np.triu(st["R2"]), iC=np.triu(st["iC"]))
+    return chains, want, None
+
+
+def _edge_regime(name, chains, N, log, nsimu):
+    """What makes a case worth running, from the restatement's oracle chains alone (the conditions of tests/test_gpu_every_chain.py's edge branch)."""
+    import edge_problems as ep
+    ckw = _edge_case(name)[0]
+    scam, ram = ckw.get("method") == "scam", ckw.get("method") == "ram"
+    cc = [ch.ch.contents for ch in chains]
+    acc = np.array([ch.accepted for ch in chains])
+    theta = np.array([ch.theta for ch in chains])
+    assert acc.shape == (N, nsimu) and np.isfinite(theta).all()
+    rate = acc[:, 1:].mean()
+    rate1 = 1.0 - sum(c.drtries for c in cc) / (N * (nsimu - 1.0)) if ckw.get("drscale") else rate
+    if name.endswith("sub"):
+        ss1 = np.array([c.ss1 for c in cc])
+        assert ep.is_subnormal(ss1).all() and len(np.unique(ss1)) == N, (ss1.min(), ss1.max(), len(np.unique(ss1)))
+        if scam:                                                # (an iteration of SCAM nearly always moves: the last component's alpha, as tests/test_gpu_every_chain.py has it)
+            a = np.minimum(np.array([np.ctypeslib.as_array(c.alpha_trace, shape=(nsimu,))[1:] for c in cc]), 1.0).mean()
+            assert rate > 0.9 and 0.5 < a < 0.9, (rate, a)
+        else:
+            assert 0.1 < rate1 < 0.5, rate1
+        if ram:
+            assert len(log) == 6 and all(ok and not n for _, n, ok in log), log        # every tick adapted
+        return
+    ssinf, ssnan, nprop = (np.array([getattr(c, k) for c in cc], dtype=np.int64) for k in ("n_ss_inf", "n_ss_nan", "nprop"))
+    tiles = [slice(t, t + 64) for t in range(0, N - 63, 64)]
+    print("%s: first-stage rate %.3f, ss = +inf %.4f, NaN %.4f of %d proposals%s" % (name, rate1, ssinf.sum() / nprop.sum(), ssnan.sum() / nprop.sum(), nprop.sum(),
+                                                                                    "; RAM ticks (iteration, NaN alphas, adapted): %s" % log if ram else ""))
+    assert all(ssnan[t].any() for t in tiles) and all(ssinf[t].any() for t in tiles)
+    if scam:
+        assert ssinf.sum() > 0 and ssnan.sum() > 0
+    else:
+        assert 0.1 < rate1 < 0.75, rate1
+        assert ssinf.sum() >= 0.01 * nprop.sum() and ssnan.sum() >= 0.005 * nprop.sum()
+    if ram:
+        # Pooled RAM folds every chain's sign(a) x x' into one statistic (pooled_ram_tick): ONE chain whose alpha is NaN at the tick's iteration
+        # makes every entry NaN, and the engine refuses to go on (pooled_reduce: error -46).  A tick that adapted comes first, then the one
+        # with a NaN alpha in a chain or two of two hundred
+        assert len(log) >= 2 and all(ok and n == 0 for _, n, ok in log[:-1]) and not log[-1][2] and 0 < log[-1][1] < 5, log
+
+
+EDGE_CASES = [f + "_" + h for f in ("am24", "am50", "dr24", "ram50ks", "ram50w2", "scam30") for h in ("ovf", "sub")]
+
+
+@pytest.mark.parametrize("name", EDGE_CASES)
+def test_pooled_matrix_core_kernels_at_infinite_nan_and_subnormal_sums_of_squares(oracle, name, monkeypatch):
+    """The Gaussian target on the f64 matrix cores -- pooled_mfma_kernel (AM at npar 24 and 50, delayed rejection at 24), pooled RAM on
+    pooled_mfma_ks_kernel and pooled_mfma_kernel<false, true> (50), scam_pooled_kernel (30) -- where a row of Lam v rounds to +-inf (ss = +inf, or
+    NaN from inf - inf in two partial chains) and where every product is subnormal: the order is defined to equal mcxt_ss_gauss's fma chain, and a
+    flush to zero or a wider internal accumulator would show here and nowhere else.  EVERY chain against the restatement: state, accept sequence,
+    ss1 and the last alpha (a NaN equals a NaN whatever its sign and payload, everything else bit for bit), stream position; the shared factor.
+    Pooled RAM at overflow: the run ends with error -46 at the first tick whose iteration has a NaN alpha in any chain (DESIGN.md section 7);
+    everything up to the iteration before is compared, then the refusal itself."""
+    import edge_problems as ep
+    from mcmcf90_amd import engine_from_problem, McmcError
+    ckw, pkw, N, env, kernel = _edge_case(name)
+    chains, want, log = _edge_restate(oracle, name)
+    refused = log[-1][0] if log and not log[-1][2] else 0       # the iteration of the tick the engine must refuse
+    nsimu = refused - 1 if refused else ckw["nsimu"]
+    try:
+        _edge_regime(name, chains, N, log, nsimu)               # ... before the engine is touched
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1)
+        e.init(); e.run(min(57, nsimu - 2)); e.run(nsimu)
+        assert e.last_kernel() == kernel, e.last_kernel()
+        theta, masks, scal = e.theta(), e.accept_masks(), e.scalars()
+        rng = np.array([e.rng(c)[0] for c in range(N)], dtype=np.uint64)
+        got = {"R": np.triu(e.pooled()[3]), "U": e.pooled()[3]}
+        if "std" in want:
+            got["std"] = e.qcovstd(0)
+        if "R2" in want:
+            got["R2"], got["iC"] = (np.triu(a) for a in e.dr_state(0))
+        tot = e.totals()
+        if refused:
+            with pytest.raises(McmcError, match="non-finite pooled statistic at iteration %d" % refused):
+                e.run()
+        e.close()
+        c = np.arange(N)
+        acc = ((masks[:, c // 64] >> (c % 64).astype(np.uint64)) & np.uint64(1)).astype(np.uint8).T
+        np.testing.assert_array_equal(acc[:, :nsimu], np.array([ch.accepted for ch in chains]))
+        np.testing.assert_array_equal(_bits(theta), _bits(np.array([ch.theta for ch in chains])))
+        cc = [ch.ch.contents for ch in chains]
+        assert ep.same_bits_or_nan(scal[:, 0], np.array([k.ss1 for k in cc])).all()
+        assert ep.same_bits_or_nan(scal[:, 3], np.array([k.alpha12 for k in cc])).all()
+        np.testing.assert_array_equal(rng, np.array([k.rng.n for k in cc], dtype=np.uint64))
+        for k, v in want.items():
+            assert np.isfinite(v).all(), k
+            np.testing.assert_array_equal(_bits(got[k]), _bits(v), err_msg=k)
+        assert tot["stayed"] == sum(k.stayed for k in cc)
+        assert not tot["status"] & 2                            # (no tick was skipped for a Gram matrix that is not positive definite)
+    finally:
+        for ch in chains:
+            ch.close()
