@@ -391,6 +391,68 @@ int mcmcx_samples_cov_dev(mcmcx_handle h, int32_t s0, int32_t ns, const double *
  * be NULL (no counterpart in the reference) */
 int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, double *cov, double *corr);
 
+/* ---- marginal and pairwise joint histograms of the retained samples, counted on the device where the ring lies (no counterpart in
+ * the reference, whose toolchain draws its hist / dens / pairs panels from a chain file): the density of every field and of pairs of
+ * fields without moving the window.  A histogram is a vector of integers and depends on no order of summation, so the results are
+ * exact; the definition is restated in numpy by tests/hist_ref.py:
+ *   Window: retained samples s0 .. s0 + ns - 1 (ns >= 1) of ALL nchains chains; n = ns * nchains values per field, as int64_t.  The
+ *   padding lanes of the last tile are never counted.
+ *   Key order: everything is in the order of the keys of mcmcx_samples_order_stats above -- the IEEE order on doubles that are no
+ *   NaN, with -0.0 < +0.0, negative NaNs below everything and positive NaNs above.
+ *   Edges: edges[nfields][nbins + 1], host memory, 1 <= nbins <= MCMCX_HIST_MAXBINS.  Within a field the edges are non-decreasing by
+ *   key; equal neighbours are allowed and give an empty bin, +-inf is allowed; a NaN edge or a decreasing pair is refused.
+ *   Cell: cell_f(x) is the number of edges e_i of field f with key(e_i) <= key(x), 0 .. nbins + 1.  Cell 0 is below e_0; cell b,
+ *   1 <= b <= nbins, is e_{b-1} <= x < e_b -- left-closed and right-open, the last bin too, unlike np.histogram; cell nbins + 1 is at
+ *   or above e_nbins.  Positive NaNs land in cell nbins + 1, negative NaNs in cell 0.
+ *   1-D: out[nfields][nbins + 2] int64, the number of window values of field f in each cell.  The cells of a field sum to n, and the
+ *   running sum through cell b equals lt_f(e_b) of mcmcx_samples_counts.
+ *   2-D: pairs[npairs][2] holds field indices in 0 .. nfields - 1, 1 <= npairs <= MCMCX_HIST2_MAXPAIRS; j == k and repeated pairs
+ *   are allowed.  1 <= nbins <= MCMCX_HIST2_MAXBINS, the edge table has the same layout (all nfields rows).
+ *   out[npairs][nbins + 2][nbins + 2] counts the (sample, chain) points with cell_j(x_j) = a and cell_k(x_k) = b at [a][b]: summing
+ *   over b gives field j's 1-D result, summing over a field k's.  96 bins keep (nbins + 2)^2 32-bit counters and both edge rows
+ *   (40 KB) well inside a workgroup's default 64 KiB of LDS.
+ *   Both results are additive over disjoint chain sets; nothing collective happens here.
+ *   Uniform edges of one field (mcmcx_samples_hist_edges: pure host), without contraction:
+ *     e_i = lo + (hi - lo) * ((double)i / nbins) for i < nbins, e_nbins = hi
+ *   Density (mcmcx_samples_hist_density: pure host), n being the sum of the field's nbins + 2 cells:
+ *     density_b = (double)count_b / ((double)n * (e_b - e_{b-1})),  1 <= b <= nbins;  an empty-width bin gives the IEEE answer.
+ * How: one pass over the window in whole rows; the field's edge keys are staged in LDS, the cell comes from a binary search over
+ * them, the counters are 32-bit in LDS (a block never counts 2**31 values) and are flushed with 64-bit integer atomics to the zeroed
+ * table; the 2-D kernel gives each workgroup one pair and reads both fields' rows together.  No float atomic.  No sampling kernel and
+ * no state of the run is touched: a run with these calls in the middle is the same run.  edges and pairs are host memory in every
+ * form and are staged during the call, so they need only stay valid until it returns.  The host forms copy the result and
+ * synchronise; the _dev forms write into the caller's DEVICE buffer, asynchronous on the engine's stream.  Device scratch is the
+ * readers' one buffer: the edge keys and, for the host forms, the table.  Refused with -52 (the reason in mcmcx_last_error) on the
+ * host, before anything is launched or allocated -- first what the arguments alone decide: a null output, edge table or pair list,
+ * nbins or npairs out of range, a NaN or decreasing edge (of the first field's row; of the others once nfields is known), a pair
+ * index outside 0 .. nfields - 1; then a null handle, an engine that is not inited, sampling off, ns < 1, a window outside the
+ * retained samples. */
+#define MCMCX_HIST_MAXBINS 1024
+#define MCMCX_HIST2_MAXBINS 96
+#define MCMCX_HIST2_MAXPAIRS 64
+/* the 1-D table of every field to host memory, host_out[nfields][nbins + 2] (no counterpart in the reference) */
+int mcmcx_samples_hist(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges /* [nfields][nbins + 1] host */,
+                       int64_t *host_out);
+/* ... into a device buffer of nfields x (nbins + 2) 64-bit integers, asynchronous on the engine's stream (no counterpart in the
+ * reference) */
+int mcmcx_samples_hist_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges, void *dev_out);
+/* the 2-D tables of npairs pairs of fields to host memory, host_out[npairs][nbins + 2][nbins + 2] (no counterpart in the reference) */
+int mcmcx_samples_hist2(mcmcx_handle h, int32_t s0, int32_t ns, int32_t npairs, const int32_t *pairs /* [npairs][2] host */,
+                        int32_t nbins, const double *edges /* [nfields][nbins + 1] host */, int64_t *host_out);
+/* ... into a device buffer of npairs x (nbins + 2)^2 64-bit integers, asynchronous on the engine's stream (no counterpart in the
+ * reference) */
+int mcmcx_samples_hist2_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t npairs, const int32_t *pairs, int32_t nbins,
+                            const double *edges, void *dev_out);
+/* nbins + 1 uniform edges of one field from lo to hi.  Pure host, no handle, no device; refuses (-52) a null output, nbins outside
+ * 1 .. MCMCX_HIST_MAXBINS, a lo or hi that is not finite, lo >= hi and a result that is not non-decreasing (hi - lo overflows)
+ * (no counterpart in the reference) */
+int mcmcx_samples_hist_edges(double lo, double hi, int32_t nbins, double *edges_out);
+/* the finish: 1-D counts[nfields][nbins + 2] (one engine's, or the sum of several) and their edges -> density_out[nfields][nbins].
+ * Pure host, no handle, no device; refuses (-52) a null argument, nfields < 1, nbins outside 1 .. MCMCX_HIST_MAXBINS (no
+ * counterpart in the reference) */
+int mcmcx_samples_hist_density(const int64_t *counts, const double *edges, int32_t nfields, int32_t nbins,
+                               double *density_out /* [nfields][nbins] */);
+
 /* Pooled mode across several GPUs: at every adaptation tick the engine writes its local moment vector
  * (mcmcx_pooled_moments_len doubles) to dev_buf, synchronises its stream and calls fn(user); fn must sum dev_buf
  * over all ranks in place (an RCCL all-reduce) and return after the result is visible.  Without a hook the local
@@ -451,6 +513,15 @@ int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int
  * counts into the ring; this can.  shift: [nfields] host or NULL.  Refusals are -51. */
 int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, const double *shift,
                             double *out);
+/* The histograms' own kernels on a caller's array (no counterpart in the reference; tests only): values[ns][nfields][nchains] host is
+ * laid out as a store of ns slots and ceil(nchains / 64) tiles, the padding lanes of the last tile filled with NaN by this entry (a
+ * kernel that counted them would show them in the last cell); out1[nfields][nbins + 2] takes the 1-D table, out2[npairs][nbins + 2]
+ * [nbins + 2] the 2-D tables of `pairs`; either may be NULL (then npairs and pairs are not looked at, or nbins may reach
+ * MCMCX_HIST_MAXBINS).  chunk = 0 is the default number of window samples per block, a small chunk forces several window chunks per
+ * tile.  A run cannot put +-0, +-inf, NaNs, denormals or values equal to an edge into the ring; this can.  Refusals are -52, what
+ * the arguments decide before a device is looked for. */
+int mcmcx_debug_samples_hist(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t nbins,
+                             const double *edges, int32_t npairs, const int32_t *pairs, int32_t chunk, int64_t *out1, int64_t *out2);
 /* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
  * inverse != 0 the bits whose key x's bits are.  Needs no device. */
 int64_t mcmcx_debug_quant_key(double x, int32_t inverse);

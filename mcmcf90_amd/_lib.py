@@ -133,6 +133,15 @@ SYMBOLS["mcmcx_samples_cov"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP,
 SYMBOLS["mcmcx_samples_cov_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_void_p])
 SYMBOLS["mcmcx_samples_cov_finish"] = (C.c_int, [_DP, C.c_int32, _DP, _DP, _DP])
 SYMBOLS["mcmcx_debug_samples_cov"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP])
+# marginal and pairwise joint histograms of the store; mcmcx_samples_hist_edges and mcmcx_samples_hist_density are pure host
+SYMBOLS["mcmcx_samples_hist"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _LP])
+SYMBOLS["mcmcx_samples_hist_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_void_p])
+SYMBOLS["mcmcx_samples_hist2"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _DP, _LP])
+SYMBOLS["mcmcx_samples_hist2_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _DP, C.c_void_p])
+SYMBOLS["mcmcx_samples_hist_edges"] = (C.c_int, [C.c_double, C.c_double, C.c_int32, _DP])
+SYMBOLS["mcmcx_samples_hist_density"] = (C.c_int, [_LP, _DP, C.c_int32, C.c_int32, _DP])
+SYMBOLS["mcmcx_debug_samples_hist"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, _IP, C.c_int32,
+                                                 _LP, _LP])
 
 _lib = None
 

@@ -29,6 +29,7 @@
 #include "mcx_host_samples.hpp"
 #include "mcx_host_diag.hpp"
 #include "mcx_host_quant.hpp"
+#include "mcx_host_hist.hpp"
 #include "mcx_host_cov.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
@@ -1109,6 +1110,56 @@ int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, d
 }
 
 
+// ------------------------------------------------------------------ marginal and joint histograms of the store (mcx_host_hist.hpp)
+int mcmcx_samples_hist_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges, void *dev_out)
+{
+    int rc = hist_check(h, s0, ns, false, 0, nullptr, nbins, edges, dev_out, "mcmcx_samples_hist_dev"); if (rc) return rc;
+    return hist_engine(h, s0, ns, nbins, edges, 0, nullptr, (unsigned long long *)dev_out, nullptr);
+}
+
+int mcmcx_samples_hist(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges, int64_t *host_out)
+{
+    int rc = hist_check(h, s0, ns, false, 0, nullptr, nbins, edges, host_out, "mcmcx_samples_hist"); if (rc) return rc;
+    unsigned long long *staged = nullptr;
+    if ((rc = hist_engine(h, s0, ns, nbins, edges, 0, nullptr, nullptr, &staged))) return rc;
+    return samples_fetch(h, host_out, staged, hist_table_words(samples_nfields(h), 0, nbins) * sizeof(int64_t));
+}
+
+int mcmcx_samples_hist2_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t npairs, const int32_t *pairs, int32_t nbins,
+                            const double *edges, void *dev_out)
+{
+    int rc = hist_check(h, s0, ns, true, npairs, pairs, nbins, edges, dev_out, "mcmcx_samples_hist2_dev"); if (rc) return rc;
+    return hist_engine(h, s0, ns, nbins, edges, npairs, pairs, (unsigned long long *)dev_out, nullptr);
+}
+
+int mcmcx_samples_hist2(mcmcx_handle h, int32_t s0, int32_t ns, int32_t npairs, const int32_t *pairs, int32_t nbins, const double *edges,
+                        int64_t *host_out)
+{
+    int rc = hist_check(h, s0, ns, true, npairs, pairs, nbins, edges, host_out, "mcmcx_samples_hist2"); if (rc) return rc;
+    unsigned long long *staged = nullptr;
+    if ((rc = hist_engine(h, s0, ns, nbins, edges, npairs, pairs, nullptr, &staged))) return rc;
+    return samples_fetch(h, host_out, staged, hist_table_words(samples_nfields(h), npairs, nbins) * sizeof(int64_t));
+}
+
+int mcmcx_samples_hist_edges(double lo, double hi, int32_t nbins, double *edges_out)
+{
+    if (!edges_out) return fail(-52, "mcmcx_samples_hist_edges: null output");
+    if (nbins < 1 || nbins > MCMCX_HIST_MAXBINS) return fail(-52, "mcmcx_samples_hist_edges: " + std::to_string(nbins) +
+        " bins, outside 1 .. " + std::to_string(MCMCX_HIST_MAXBINS));
+    return hist_edges(lo, hi, nbins, edges_out);
+}
+
+int mcmcx_samples_hist_density(const int64_t *counts, const double *edges, int32_t nfields, int32_t nbins, double *density_out)
+{
+    if (!counts || !edges || !density_out) return fail(-52, "mcmcx_samples_hist_density: null argument");
+    if (nfields < 1) return fail(-52, "mcmcx_samples_hist_density: nfields < 1");
+    if (nbins < 1 || nbins > MCMCX_HIST_MAXBINS) return fail(-52, "mcmcx_samples_hist_density: " + std::to_string(nbins) +
+        " bins, outside 1 .. " + std::to_string(MCMCX_HIST_MAXBINS));
+    hist_density(counts, edges, nfields, nbins, density_out);
+    return 0;
+}
+
+
 int32_t mcmcx_pooled_moments_len(mcmcx_handle h) { return h ? 1 + h->d + h->P : -1; }
 
 static int pooled_vec_len(const mcmcx_engine *h, int kind) { return kind == 2 ? 2 + h->P : 1 + h->d + h->P + (kind == 1 ? 1 : 0); }
@@ -1323,6 +1374,51 @@ int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, in
     int rc = cov_launch(W, w, shift, dout, 0); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(0));
     HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the histograms' own kernels on a caller's array: a store of ns slots, ceil(nchains / 64) tiles and nfields fields filled from
+// values[ns][nfields][nchains]; the padding lanes of the last tile hold NaN, which a kernel that counted them would put into the last cell
+int mcmcx_debug_samples_hist(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t nbins,
+                             const double *edges, int32_t npairs, const int32_t *pairs, int32_t chunk, int64_t *out1, int64_t *out2)
+{
+    const char *who = "mcmcx_debug_samples_hist";
+    if (!values) return fail(-52, std::string(who) + ": null values");
+    int rc = hist_check_args(nbins, out2 ? MCMCX_HIST2_MAXBINS : MCMCX_HIST_MAXBINS, edges, out1 ? (void *)out1 : (void *)out2, who);
+    if (rc) return rc;
+    if (out2 && (rc = hist_check_npairs(npairs, pairs, who))) return rc;
+    if (nchains < 1 || nfields < 1 || ns < 1 || chunk < 0) return fail(-52, std::string(who) + ": nchains, nfields, ns < 1 or chunk < 0");
+    if ((rc = hist_check_edges(edges, nfields, nbins, who))) return rc;
+    if (out2 && (rc = hist_check_pairs(pairs, npairs, nfields, who))) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const int T = (nchains + 63) / 64;
+    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
+    std::vector<double> host(words, std::nan(""));
+    for (int s = 0; s < ns; ++s)
+        for (int f = 0; f < nfields; ++f)
+            for (int c = 0; c < nchains; ++c)
+                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
+                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
+    const size_t m = hist_key_words(nfields, nbins), n1 = hist_table_words(nfields, 0, nbins);
+    const size_t n2 = out2 ? hist_table_words(nfields, npairs, nbins) : 0;
+    DevBufs g;
+    double *store = nullptr; unsigned long long *w = nullptr;
+    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, (m + std::max(n1, n2)) * 8));
+    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
+    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
+    const QuantWin A = hist_window(W, chunk);
+    if (out1) {
+        if ((rc = hist_launch(A, w, nbins, edges, 0, nullptr, w + m, 0))) return rc;
+        HIPCHK(hipStreamSynchronize(0));
+        HIPCHK(hipMemcpy(out1, w + m, n1 * 8, hipMemcpyDeviceToHost));
+    }
+    if (out2) {
+        if ((rc = hist_launch(A, w, nbins, edges, npairs, pairs, w + m, 0))) return rc;
+        HIPCHK(hipStreamSynchronize(0));
+        HIPCHK(hipMemcpy(out2, w + m, n2 * 8, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

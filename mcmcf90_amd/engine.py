@@ -126,6 +126,34 @@ def samples_quantile_ranks(n, probs):
     return ranks, frac
 
 
+HIST_MAXBINS, HIST2_MAXBINS, HIST2_MAXPAIRS = 1024, 96, 64
+
+
+def samples_hist_edges(lo, hi, nbins):
+    """nbins + 1 uniform edges of one field, e_i = lo + (hi - lo) * (i / nbins) and e_nbins = hi: mcmcx_samples_hist_edges, pure host
+    arithmetic, no engine and no device."""
+    L = _lib.load()
+    e = np.zeros(max(int(nbins), 0) + 1)
+    if L.mcmcx_samples_hist_edges(float(lo), float(hi), int(nbins), _dp(e)) < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return e
+
+
+def samples_hist_density(counts, edges):
+    """[nfields][nbins] densities from 1-D counts[nfields][nbins + 2] (one engine's, or the sum of several engines') and their
+    edges[nfields][nbins + 1]: count_b / (n (e_b - e_{b-1})), n the sum of the field's cells, the two outer cells included --
+    mcmcx_samples_hist_density, pure host arithmetic, no engine and no device."""
+    L = _lib.load()
+    c, e = _i64(counts), _f64(edges)
+    if c.ndim != 2 or e.ndim != 2 or c.shape[0] != e.shape[0] or c.shape[1] != e.shape[1] + 1 or e.shape[1] < 2:
+        raise McmcError("samples_hist_density: counts must be [nfields][nbins + 2] and edges [nfields][nbins + 1], got %s and %s"
+                        % (c.shape, e.shape))
+    d = np.zeros((c.shape[0], e.shape[1] - 1))
+    if L.mcmcx_samples_hist_density(_lp(c), _dp(e), int(c.shape[0]), int(e.shape[1] - 1), _dp(d)) < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return d
+
+
 def sample_field_names(npar, nycol=1):
     """Names of a sample's fields, in the store's order."""
     ny = int(nycol)
@@ -525,6 +553,54 @@ class Engine:
             out["probs"] = _f64(probs).ravel().copy()
             out["quantiles"] = self.samples_quantiles(out["probs"], s0, ns)
         return out
+
+    # --- marginal and pairwise joint histograms of the retained samples (mcmcx_samples_hist / _hist2)
+    def _hist_args(self, s0, ns, edges, pairs, who):
+        """(ns, nfields, edges[nfields][nbins + 1], pairs[npairs][2] or None) of a histogram call"""
+        ns, _, _, nf = self._window(s0, ns)
+        ed = _f64(edges)
+        if ed.ndim != 2 or ed.shape[0] != nf or ed.shape[1] < 2:
+            raise McmcError("%s: edges must be [nfields = %d][nbins + 1], got %s" % (who, nf, ed.shape))
+        if pairs is None:
+            return ns, nf, ed, None
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32))
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise McmcError("%s: pairs must be [npairs][2], got %s" % (who, pr.shape))
+        return ns, nf, ed, pr
+
+    def samples_hist(self, edges, s0=0, ns=None):
+        """int64 [nfields][nbins + 2]: how many of the ns x nchains values of field f in retained samples s0 .. s0 + ns - 1 lie in each
+        cell of edges[f] (include/mcmcx.h has the definition: cell 0 below the first edge, cell b = [e_{b-1}, e_b), cell nbins + 1 at or
+        above the last).  Exact and additive over engines that hold disjoint chains; `samples_hist_density` finishes it."""
+        ns, nf, ed, _ = self._hist_args(s0, ns, edges, None, "samples_hist")
+        a = np.zeros((nf, ed.shape[1] + 1), dtype=np.int64)
+        self._chk(self.L.mcmcx_samples_hist(self.h, int(s0), ns, int(ed.shape[1] - 1), _dp(ed), _lp(a)))
+        return a
+
+    def samples_hist_torch(self, edges, s0=0, ns=None):
+        """The same as an int64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        import torch
+        ns, nf, ed, _ = self._hist_args(s0, ns, edges, None, "samples_hist_torch")
+        return self._dev((nf, ed.shape[1] + 1),
+                         lambda p: self.L.mcmcx_samples_hist_dev(self.h, int(s0), ns, int(ed.shape[1] - 1), _dp(ed), p)).view(torch.int64)
+
+    def samples_hist2(self, pairs, edges, s0=0, ns=None):
+        """int64 [npairs][nbins + 2][nbins + 2]: for every pair (j, k) of field indices the number of (sample, chain) points of the
+        window with field j in cell a of edges[j] and field k in cell b of edges[k], at [a][b]; at most HIST2_MAXBINS bins and
+        HIST2_MAXPAIRS pairs per call.  Exact and additive over engines that hold disjoint chains."""
+        ns, nf, ed, pr = self._hist_args(s0, ns, edges, pairs, "samples_hist2")
+        a = np.zeros((pr.shape[0], ed.shape[1] + 1, ed.shape[1] + 1), dtype=np.int64)
+        self._chk(self.L.mcmcx_samples_hist2(self.h, int(s0), ns, int(pr.shape[0]), pr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             int(ed.shape[1] - 1), _dp(ed), _lp(a)))
+        return a
+
+    def samples_hist2_torch(self, pairs, edges, s0=0, ns=None):
+        """The same as an int64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        import torch
+        ns, nf, ed, pr = self._hist_args(s0, ns, edges, pairs, "samples_hist2_torch")
+        return self._dev((pr.shape[0], ed.shape[1] + 1, ed.shape[1] + 1),
+                         lambda p: self.L.mcmcx_samples_hist2_dev(self.h, int(s0), ns, int(pr.shape[0]), pr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                  int(ed.shape[1] - 1), _dp(ed), p)).view(torch.int64)
 
     # --- posterior covariance of the retained samples, on the matrix cores (mcmcx_samples_cov)
     def samples_cov_stats(self, s0=0, ns=None, shift=None):
