@@ -68,8 +68,12 @@ typedef struct mcmcx_config {
     int32_t scam_fast;     /* method = 'scam' only, opt-in (default 0 = the reference's operations): the componentwise proposal
                             * newpar = U (U'oldpar + delta e_j) (MCMC_run_scam.F90:106-115: two dgemv) is formed as
                             * newpar = oldpar + delta U(:,j) -- the same point up to the rounding of U U' = I, one column
-                            * of the rotation instead of two passes over it.  Accept sequences and states agree with the
-                            * reference-order form to rounding level, not bit for bit (tests/test_gpu_scam_fast.py). */
+                            * of the rotation instead of two passes over it.  Every kernel form computes
+                            * newpar_k = fma(delta, U(k,j), oldpar_k) with delta the sub-step's first draw, which the test oracle
+                            * restates (oracle/mcx_oracle.h, scam_fast): the engine is pinned to that restatement bit for bit on every
+                            * chain (tests/test_gpu_every_chain.py, test_gpu_pooled.py, test_gpu_scam_fast.py), and to the
+                            * reference and its reference-order form only to rounding level (same accept sequences on the
+                            * reference's fixtures, states within 1e-6; tests/test_oracle_scam_fast.py). */
 } mcmcx_config;
 
 typedef struct mcmcx_engine *mcmcx_handle;

@@ -813,11 +813,19 @@ int mcxo_chain_run(mcxo_chain *c, int upto)
             int rejall = 1;
             double *rot = work;                                      /* work has 3n doubles */
             for (int j = 0; j < n; ++j) {
+                if (c->scam_fast) {
+                    /* the engine's opt-in mcmcx_config::scam_fast: newpar = oldpar + zj U(:,j), one fused multiply-add per element;
+                     * the deviate is still the sub-step's first draw.  Not the reference's operations: equal to them only where
+                     * U'x and U y are exact, within rounding elsewhere (tests/test_oracle_scam_fast.py) */
+                    double zj = mcxo_normal(&c->rng) * c->qcovstd[j];
+                    for (int k = 0; k < n; ++k) newpar[k] = fma(zj, c->R[(size_t)j * n + k], c->oldpar[k]);
+                } else {
                 /* MCMC_propose_sc (:94-117): rotate, perturb component j, rotate back */
                 mcxo_gemv(1, n, c->R, c->oldpar, rot);
                 double zj = mcxo_normal(&c->rng) * c->qcovstd[j];
                 rot[j] = rot[j] + zj;
                 mcxo_gemv(0, n, c->R, rot, newpar);
+                }
                 c->nprop++;
                 inb = mcxo_checkbounds(&c->tgt, newpar);
                 if (!inb) { if (!g->dodr) c->bndstayed++; c->alpha12 = 0.0; reject = 1; }

@@ -101,6 +101,11 @@ typedef struct mcxo_chain {
     /* evaluated proposals (both stages, every SCAM component) whose sum of squares was +inf / NaN: the regime of the tests at
      * overflowing targets (tests/edge_problems.py), which early rejection shows nowhere else */
     int n_ss_inf, n_ss_nan;
+    /* a per-chain switch like continue_on_downdate_fail above (not in mcxo_cfg: the fixtures record that struct's fields and the
+     * reference knows no such form).  1, method = 'scam': the componentwise proposal of the engine's opt-in mcmcx_config::scam_fast,
+     * newpar_k = fma(zj, U(k,j), oldpar_k) with zj = normal * qcovstd_j drawn first, in place of U (U'oldpar + zj e_j)
+     * (MCMC_run_scam.F90:106-115); everything after the candidate is the same code.  0: the reference's operations */
+    int scam_fast;
 } mcxo_chain;
 
 mcxo_chain *mcxo_chain_create(const mcxo_cfg *cfg, const mcxo_target *tgt, const double *par0,

@@ -56,7 +56,7 @@ class Chain(C.Structure):
                 ("continue_on_downdate_fail", C.c_int), ("qcovstd", _DP), ("erstayed", C.c_int),
                 ("ny", C.c_int), ("ss1v", C.c_double * 32), ("sigma2v", C.c_double * 32), ("nobsv", C.c_int * 32),       # MCXO_NYMAX
                 ("trmv_desc", C.c_int), ("last_u", _DP), ("n_calcR", C.c_int), ("svd_floored", C.c_int),
-                ("n_ss_inf", C.c_int), ("n_ss_nan", C.c_int)]
+                ("n_ss_inf", C.c_int), ("n_ss_nan", C.c_int), ("scam_fast", C.c_int)]
 
 
 _lib = None
@@ -172,8 +172,9 @@ class Result:
     pass
 
 
-def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_downdate_fail=False):
-    """Run one chain through the oracle; returns the reference-visible outputs."""
+def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_downdate_fail=False, scam_fast=False):
+    """Run one chain through the oracle; returns the reference-visible outputs.
+    scam_fast (method = 'scam'): the engine's opt-in componentwise proposal oldpar + zj U(:,j), mcx_oracle.h."""
     L = lib()
     tgt = prob.ctarget()
     cm = np.asfortranarray(prob.cmat0)            # column-major like the reference
@@ -183,6 +184,7 @@ def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_dow
         raise RuntimeError("could not factor the initial covariance")
     try:
         ch.contents.continue_on_downdate_fail = 1 if continue_on_downdate_fail else 0
+        ch.contents.scam_fast = 1 if scam_fast else 0
         rc = L.mcxo_chain_run(ch, cfg.nsimu if upto is None else upto)
         c = ch.contents
         n, ns = prob.npar, c.simuind
@@ -225,7 +227,7 @@ class LiveChain:
     """An oracle chain kept alive between segments, whose proposal factor can be replaced from outside
     (used to restate the engine's pooled mode, where adaptation happens across chains)."""
 
-    def __init__(self, cfg, prob, seed=0x6D636D63, chain_id=0):
+    def __init__(self, cfg, prob, seed=0x6D636D63, chain_id=0, scam_fast=False):
         L = lib()
         self.cfg, self.prob, self.n = cfg, prob, prob.npar
         self._tgt = prob.ctarget()
@@ -234,6 +236,7 @@ class LiveChain:
                                          _dp(prob.sigma2v), prob.nobsv.ctypes.data_as(C.POINTER(C.c_int)), prob.ny, seed, chain_id)
         if not self.ch:
             raise RuntimeError("could not factor the initial covariance")
+        self.ch.contents.scam_fast = 1 if scam_fast else 0
 
     def run(self, upto):
         rc = lib().mcxo_chain_run(self.ch, upto)

@@ -14,8 +14,14 @@ matutils.F90:283-338), bit for bit.  The regime of every case is asserted from t
 rate of 0.1..0.5 for the Gaussian and response-column targets, so that lanes accept at different iterations; the last component's alpha for
 SCAM; the high-acceptance regime for banana and for the sigma2 update below shape one, which allows no other; bounds that bite; the three
 burn-in branches side by side.  (Pooled mode has one factor for all
-chains and its restatement tests compare all of them; method = 'ram' is tests/test_gpu_ram_every_chain.py; scam_fast is an opt-in form
-the oracle does not restate.)"""
+chains and its restatement tests compare all of them; method = 'ram' is tests/test_gpu_ram_every_chain.py.)
+
+fast=1 is mcmcx_config::scam_fast, the opt-in componentwise proposal cand_k = fma(zj, U(k,j), theta_k): the oracle restates it behind a
+per-chain switch (oracle/mcx_oracle.h, tied to the reference's fixtures by tests/test_oracle_scam_fast.py), and every form that takes it --
+the lane kernels at one to eight waves, scam_pooled_kernel<per-chain> with each lane's own column of E.Rf at three layouts of its waves,
+the lane kernels that form falls back to under bounds and priors, step_kernel_cols<scam> -- is held to it on every chain like the rest.
+A rounding-level tolerance cannot see a wrong column element in a ragged last block, a pad row that is not zero or an unfused multiply-add;
+the accept sequence of some chain moves within a few hundred sub-steps of any of them."""
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -38,6 +44,10 @@ BURN_TICKS = (20, 40, 60)
 def P(kind, d, **opt):
     """A problem: target kind, npar and what departs from the plain adaptive Metropolis run (hashable: the key of the oracle's cache)."""
     return (kind, d, tuple(sorted(opt.items())))
+
+
+def _fast(prob):
+    return int(dict(prob[2]).get("fast", 0))                    # mcmcx_config::scam_fast on the engine, scam_fast=True on the oracle's chains
 
 
 def _bounded(prob):
@@ -135,7 +145,7 @@ def _oracle_all(oracle, prob):
         cfg = oracle.make_cfg(**ckw); pr = oracle.Problem(**pkw)
         oracle.lib()
         with ThreadPoolExecutor(8) as pool:
-            rs = list(pool.map(lambda c: oracle.run_chain(cfg, pr, chain_id=CHAIN_ID0 + c), range(nch)))
+            rs = list(pool.map(lambda c: oracle.run_chain(cfg, pr, chain_id=CHAIN_ID0 + c, scam_fast=bool(_fast(prob))), range(nch)))
         assert len(rs) == nch and all(r.simuind == nsimu and r.rc == 0 for r in rs)
         o = dict(theta=np.array([r.theta for r in rs]), acc=np.array([r.accepted for r in rs], dtype=np.uint8),
                  scal=np.array([[r.ss1, r.sspri1, r.sigma2, r.alpha12] for r in rs]), rng=np.array([r.rng_n for r in rs], dtype=np.uint64),
@@ -314,6 +324,24 @@ def _cases():
     for e in ("ovf:15:0.5", SUB):
         xsc = G(12, method="scam", nsimu=120, edge=e)
         add("scam1", xsc, "scam_kernel", dict(MCMCX_SCAM_WAVES="1")); add("scam4", xsc, "scam_mw_kernel<4>", dict(MCMCX_SCAM_WAVES="4"))
+    # ---- scam_fast, cand = fma(zj, U(:,j), theta), against the oracle's restatement of it.  The lane kernels at one, two, four and eight waves:
+    f12 = G(12, method="scam", nsimu=120, fast=1)
+    for nw, k in ((1, "scam_kernel"), (2, "scam_mw_kernel<2>"), (4, "scam_mw_kernel<4>"), (8, "scam_mw_kernel<8>")):
+        add("fast_lanes%d" % nw, f12, k, dict(MCMCX_SCAM_FAST_LANES="1", MCMCX_SCAM_WAVES=str(nw)))
+    # ... the matrix-core form the plan takes by itself, every lane with its own chain's column of E.Rf, at three layouts of its waves:
+    # npar 12 is one ragged block (the four group waves alone), 40 three leftover blocks and no block wave, 67 four block waves and one
+    # leftover block with a pad row (d4 = 68).  40 and 67 have one tick and a cut right behind it; 12 once more with the sigma2 update
+    PC = "scam_pooled_kernel<per-chain>"
+    add("fast_tile", f12, PC)
+    add("fast_tile", G(40, method="scam", nsimu=60, fast=1), PC); add("fast_tile", G(67, method="scam", nsimu=60, fast=1), PC)
+    add("fast_tile", G(12, method="scam", nsimu=120, fast=1, sigma2=(1.0, 11)), PC)
+    # ... what that form falls back to: bounds and priors are not its business, so the plan names a lane kernel (ten tiles: eight waves each),
+    # and both see the fast candidate
+    add("fast_fallback", G(12, method="scam", fast=1, priors=1), "scam_mw_kernel<8>"); add("fast_fallback", G(12, method="scam", fast=1, bounded=1), "scam_mw_kernel<8>")
+    add("fast_cols", P("cols", 3, method="scam", fast=1), "step_kernel_cols<scam>")
+    # ... and the matrix-core target at +inf and NaN sums of squares: T and c of the reference-order case above meet _regime's edge conditions
+    # under the fast oracle as they stand (+inf in 7.7 %, NaN in 1.1 % of the proposals, both in every full tile)
+    add("fast_tile", G(12, method="scam", nsimu=120, fast=1, edge="ovf:15:0.5"), PC)
     return C
 
 
@@ -329,7 +357,7 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     cols = prob[0] == "cols"                                    # (the recorded chain is the engine's only view of the second column)
-    e = engine_from_problem(ckw, pkw, nchains=nch, chain_id0=CHAIN_ID0, record_accept=1, record_chain=1 if cols else 0)
+    e = engine_from_problem(ckw, pkw, nchains=nch, chain_id0=CHAIN_ID0, record_accept=1, record_chain=1 if cols else 0, scam_fast=_fast(prob))
     e.init()
     for upto in cuts:
         e.run(upto)

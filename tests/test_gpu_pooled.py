@@ -193,10 +193,12 @@ def _scam_factor(oracle, state, d, condmax):
     return state
 
 
-@pytest.mark.parametrize("kind", ["gauss", "banana"])
-def test_pooled_scam_matches_restatement(oracle, kind):
+@pytest.mark.parametrize("kind,fast", [pytest.param("gauss", 0, id="gauss"), pytest.param("banana", 0, id="banana"),
+                                       pytest.param("gauss", 1, id="gauss-fast"), pytest.param("banana", 1, id="banana-fast")])
+def test_pooled_scam_matches_restatement(oracle, kind, fast):
     """method='scam' with pooled=1: one rotation U / qcovstd for all chains, re-derived at every tick from the pooled
-    covariance (scam_pooled_kernel: four waves per tile, U through the scalar cache)."""
+    covariance (scam_pooled_kernel: four waves per tile, U through the scalar cache).  fast: mcmcx_config::scam_fast against the oracle's
+    restatement of it (LiveChain(scam_fast=True): cand = fma(zj, U(:,j), theta)); nothing else in the restatement changes."""
     from mcmcf90_amd import engine_from_problem
     d, N, nsimu = 7, 150, 230
     ckw = dict(nsimu=nsimu, adaptint=100, updatesigma=0, method="scam")
@@ -205,11 +207,11 @@ def test_pooled_scam_matches_restatement(oracle, kind):
         pkw = dict(kind="gauss", npar=d, par0=np.full(d, 0.5), cmat0=0.02 * np.eye(d), mu=np.linspace(-1, 1, d), lam=np.linalg.inv(S))
     else:
         pkw = dict(kind="banana", npar=d, par0=np.zeros(d), cmat0=0.05 * np.eye(d), b=0.1)
-    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1)
+    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1, scam_fast=fast)
     e.init(); e.run()
     cfg = oracle.make_cfg(**dict(ckw, doadapt=0))
     prob = oracle.Problem(**pkw)
-    chains = [oracle.LiveChain(cfg, prob, chain_id=c) for c in range(N)]
+    chains = [oracle.LiveChain(cfg, prob, chain_id=c, scam_fast=bool(fast)) for c in range(N)]
     state = {}
     par0, cmat0 = np.asarray(pkw["par0"], float), np.asarray(pkw["cmat0"], float)
     for tick in (100, 200, nsimu):
@@ -272,12 +274,22 @@ def test_pooled_scam_twelve_wave_layout_equals_the_sixteen_wave_layout(seed, mon
     np.testing.assert_array_equal(_bits(a[4]), _bits(b[4]))
 
 
+def _layout(d, extras, fast=0, extended=False):
+    return pytest.param(d, extras, fast, id="%d-%s%s" % (d, extras, "-fast" if fast else ""), marks=[pytest.mark.extended] if extended else [])
+
+
 @pytest.mark.slow
-@pytest.mark.parametrize("d,extras", [(40, "s2"), (64, ""), (70, "bounds"), (100, "priors"), (130, ""), (200, "bounds"), pytest.param(215, "", marks=pytest.mark.extended),
-                                      # (230: twelve fifth slots -- 25 s of oracle chains; since round 6 the twelve-wave kernel has eighteen device-side cases over its
-                                      #  whole npar range above, and 200 keeps its tie to the oracle in the default suite)
-                                      pytest.param(230, "priors", marks=pytest.mark.extended), pytest.param(200, "sixteen", marks=pytest.mark.extended), (250, "replicated")])
-def test_pooled_scam_wave_layouts(oracle, d, extras, monkeypatch):
+@pytest.mark.parametrize("d,extras,fast", [_layout(40, "s2"), _layout(64, ""), _layout(70, "bounds"), _layout(100, "priors"), _layout(130, ""), _layout(200, "bounds"),
+                                           _layout(215, "", extended=True),
+                                           # (230: twelve fifth slots -- 25 s of oracle chains; since round 6 the twelve-wave kernel has eighteen device-side cases over its
+                                           #  whole npar range above, and 200 keeps its tie to the oracle in the default suite)
+                                           _layout(230, "priors", extended=True), _layout(200, "sixteen", extended=True), _layout(250, "replicated"),
+                                           # mcmcx_config::scam_fast on the same splits, against the restatement with the oracle's fast chains: 200 is
+                                           # scam_pooled12_kernel, the kernel of bench.py's c5_pooled_fast row; with bounds the candidate makes its round trip
+                                           # through global memory; 250 runs the per-chain lane kernels on copies of the one rotation
+                                           _layout(40, "", 1), _layout(70, "", 1), _layout(130, "", 1), _layout(200, "", 1), _layout(200, "sixteen", 1, extended=True),
+                                           _layout(100, "bounds", 1), _layout(250, "replicated", 1)])
+def test_pooled_scam_wave_layouts(oracle, d, extras, fast, monkeypatch):
     """Every split of scam_pooled_kernel's output blocks over its waves: d=40 three leftover blocks and no block wave,
     64 four block waves and nothing left over, 70 / 100 four block waves + one / three leftover blocks, 130 eight + one;
     200 / 215 / 230: scam_pooled12_kernel, twelve block waves with four / eight / twelve fifth slots (the last one on the
@@ -299,12 +311,12 @@ def test_pooled_scam_wave_layouts(oracle, d, extras, monkeypatch):
         pkw.update(lo=np.full(d, -0.2), hi=np.full(d, 0.45))
     if extras == "priors":
         pkw.update(pri_mu=np.zeros(d), pri_sig=np.where(np.arange(d) % 3 == 0, 0.0, 0.5))
-    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1)
+    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1, scam_fast=fast)
     e.init(); e.run()
     assert e.last_kernel() == ("scam_mw_kernel<8>" if d > 240 else "scam_pooled12_kernel" if (d >= 193 and extras != "sixteen") else "scam_pooled_kernel"), e.last_kernel()
     cfg = oracle.make_cfg(**dict(ckw, doadapt=0))
     prob = oracle.Problem(**pkw)
-    chains = [oracle.LiveChain(cfg, prob, chain_id=c) for c in range(N)]
+    chains = [oracle.LiveChain(cfg, prob, chain_id=c, scam_fast=bool(fast)) for c in range(N)]
     state = {}
     par0, cmat0 = np.asarray(pkw["par0"], float), np.asarray(pkw["cmat0"], float)
     for t in [t for t in (3, 6) if t < nsimu] + [nsimu]:
@@ -329,9 +341,10 @@ def test_pooled_scam_wave_layouts(oracle, d, extras, monkeypatch):
     e.close()
 
 
-def _check_pooled_scam_against_restatement(oracle, seed):
+def _check_pooled_scam_against_restatement(oracle, seed, scam_fast=0):
     """A random pooled SCAM configuration (one rotation for all chains, adapted from the pooled covariance every adaptint iterations) against the
-    restatement of test_pooled_scam_wave_layouts: npar 2..64, ragged tiles, condmax floors, bounds, priors, the sigma2 update, a cut run."""
+    restatement of test_pooled_scam_wave_layouts: npar 2..64, ragged tiles, condmax floors, bounds, priors, the sigma2 update, a cut run.
+    scam_fast: the engine's opt-in proposal against the oracle's fast chains."""
     from mcmcf90_amd import engine_from_problem
     r = np.random.default_rng(95000 + seed)
     d = int(r.choice([2, 3, 5, 8, 13, 16, 17, 24, 33, 40, 48, 64]))
@@ -347,12 +360,12 @@ def _check_pooled_scam_against_restatement(oracle, seed):
     if ckw["updatesigma"]: pkw.update(sigma2=0.7, nobs=30)
     if r.random() < 0.3: pkw.update(lo=np.full(d, -0.8), hi=np.full(d, 0.9))
     if r.random() < 0.3: pkw.update(pri_mu=np.zeros(d), pri_sig=np.where(np.arange(d) % 3 == 0, 0.0, 0.5))
-    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1)
+    e = engine_from_problem(ckw, pkw, nchains=N, pooled=1, record_accept=1, scam_fast=scam_fast)
     e.init(); e.run(int(r.integers(1, nsimu))); e.run()
     kernel = e.last_kernel()
     cfg = oracle.make_cfg(**dict(ckw, doadapt=0))
     prob = oracle.Problem(**pkw)
-    chains = [oracle.LiveChain(cfg, prob, chain_id=c) for c in range(N)]
+    chains = [oracle.LiveChain(cfg, prob, chain_id=c, scam_fast=bool(scam_fast)) for c in range(N)]
     try:
         state = {}
         par0, cmat0 = np.asarray(pkw["par0"], float), np.asarray(pkw["cmat0"], float)
@@ -381,6 +394,12 @@ def _check_pooled_scam_against_restatement(oracle, seed):
 @pytest.mark.parametrize("seed", range(24))
 def test_random_pooled_scam_configuration_matches_restatement(oracle, seed):
     _check_pooled_scam_against_restatement(oracle, seed)
+
+
+@pytest.mark.parametrize("seed", range(100, 112))
+def test_random_pooled_fast_scam_configuration_matches_restatement(oracle, seed):
+    """A seed range of its own with mcmcx_config::scam_fast (the 24 seeds above and their draws stay as they are)."""
+    _check_pooled_scam_against_restatement(oracle, seed, scam_fast=1)
 
 
 @pytest.mark.parametrize("waves", [1, 2], ids=["one_wave_per_simd", "two_waves_per_simd"])

@@ -105,6 +105,9 @@ ANCHOR = [
     ("scam", dict(adaptint=20), 20, 130, 50),
     ("scam", dict(adaptint=10), 50, 70, 25),
     ("scam", dict(adaptint=10), 64, 130, 25),
+    # mcmcx_config::scam_fast through host_phase_kernel<5>'s proposal (the built-in side is tied to the oracle's restatement of the fast form
+    # by test_gpu_pooled.py::test_pooled_scam_matches_restatement[banana-fast])
+    ("scam", dict(adaptint=20, scam_fast=1), 20, 130, 50),
 ]
 
 

@@ -1,9 +1,13 @@
 """mcmcx_config::scam_fast (opt-in, method = 'scam'): the componentwise proposal formed as oldpar + delta U(:,j) instead
 of the reference's U (U'oldpar + delta e_j) (MCMC_run_scam.F90:106-115).  Not the reference's operations, so not bit for
 bit its chain: what north_star asks of floating point -- the accept-index sequence identical under the fixed stream, states /
-moments within 1e-6 relative -- is what is checked here, against the reference fixtures and against the oracle
-(reference-order arithmetic).  The default (scam_fast = 0) stays the bit-exact form covered everywhere else."""
+moments within 1e-6 relative -- is what is checked here against the reference fixtures.  Every form computes
+cand_k = fma(zj, U(k,j), theta_k), which the oracle restates behind its chains' scam_fast switch (oracle/mcx_oracle.h,
+tests/test_oracle_scam_fast.py): against THAT every chain is compared bit for bit.  The default (scam_fast = 0) stays the
+bit-exact form covered everywhere else."""
 import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import pytest
 from golden_util import load, accepted_from_runlen
@@ -13,6 +17,24 @@ pytestmark = pytest.mark.gpu
 
 def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+_FAST = {}
+
+
+def _fast_oracle(oracle, key, cfg, prob, chain_id0, nch, upto=None):
+    """Chains chain_id0 .. chain_id0 + nch - 1 through the fast oracle: once per problem, shared by the forms that run it, never changed."""
+    if key not in _FAST:
+        oracle.lib()
+        with ThreadPoolExecutor(8) as pool:
+            _FAST[key] = list(pool.map(lambda c: oracle.run_chain(cfg, prob, chain_id=chain_id0 + c, upto=upto, scam_fast=True), range(nch)))
+        assert all(o.rc == 0 for o in _FAST[key])
+    return _FAST[key]
+
+
+def _accepted_all(e, nch):
+    masks, c = e.accept_masks(), np.arange(nch)
+    return ((masks[:, c // 64] >> (c % 64).astype(np.uint64)) & np.uint64(1)).astype(np.uint8).T      # [chain][iteration]
 
 
 def _kw(z):
@@ -29,7 +51,8 @@ def _kw(z):
 @pytest.mark.parametrize("waves", [1, 8, 0])          # 0: the matrix-core form (Gaussian target only; the others run the lane kernels again)
 def test_fast_scam_reproduces_the_reference_fixtures(oracle, name, waves, monkeypatch):
     """Per-chain rotations, the reference's SCAM fixtures (real reference, several adaptations each): run-length column and
-    stream position identical, the chain's rows and the final covariance / mean within 1e-6 relative."""
+    stream position identical, the chain's rows and the final covariance / mean within 1e-6 relative (the reference is another
+    arithmetic).  All 70 chains against the fast oracle: state, recorded rows, accept sequence, stream position, bit for bit."""
     from mcmcf90_amd import engine_from_problem
     if waves:
         monkeypatch.setenv("MCMCX_SCAM_WAVES", str(waves))
@@ -51,20 +74,24 @@ def test_fast_scam_reproduces_the_reference_fixtures(oracle, name, waves, monkey
     cm, mean, _ = e.chaincov(1)
     assert np.max(np.abs(np.triu(cm) - np.triu(z["chaincmat"]))) / np.max(np.abs(z["chaincmat"])) < 1e-6
     assert np.max(np.abs(mean - z["chainmean"])) / max(np.max(np.abs(z["chainmean"])), 1e-300) < 1e-6
-    # the other chains against the oracle (reference-order arithmetic): same decisions, same stream position
-    for c in (0, 64, 69):
-        o = oracle.run_chain(cfg, prob, chain_id=cid - 1 + c)
-        np.testing.assert_array_equal(e.accepted(c), o.accepted)
-        assert e.rng(c)[0] == o.rng_n
+    # every chain against the oracle's restatement of the fast form: the same bits
+    os_ = _fast_oracle(oracle, name, cfg, prob, cid - 1, 70)
+    theta, acc = e.theta(), _accepted_all(e, 70)
+    bad = []
+    for c, o in enumerate(os_):
         chc, _, _ = e.chain(c)
-        assert np.max(np.abs(chc[:, :-1] - o.chain[:, :-1]) / np.maximum(np.abs(o.chain[:, :-1]).max(axis=0), 1e-3)) < 1e-6
+        ok = (np.array_equal(acc[c], o.accepted), e.rng(c)[0] == o.rng_n, np.array_equal(_bits(theta[c]), _bits(o.theta)),
+              chc.shape == o.chain.shape and np.array_equal(_bits(chc), _bits(o.chain)))
+        if not all(ok):
+            bad.append((c, ok))
     e.close()
+    assert not bad, "chains (accept sequence, stream position, state, rows): %s" % bad[:8]
 
 
 @pytest.mark.parametrize("lanes", [0, 1], ids=["matrix_cores", "lane_kernels"])
 def test_fast_scam_config5_up_to_the_first_adaptation(oracle, lanes, monkeypatch):
     """BASELINE config 5's target (d = 200, cond 1e6), per-chain: 9 iterations x 200 componentwise proposals with the
-    initial rotation, against the oracle -- identical decisions and stream position, states to 1e-9 of their scale.  (Past an
+    initial rotation, all 70 chains against the fast oracle -- decisions, stream position and state bit for bit.  (Past an
     adaptation the d = 200 trajectory is not a function of the inputs alone, DESIGN.md section 8: no form of the
     arithmetic, this one included, can be compared there.)"""
     from mcmcf90_amd import engine_from_problem
@@ -75,13 +102,13 @@ def test_fast_scam_config5_up_to_the_first_adaptation(oracle, lanes, monkeypatch
     e = engine_from_problem(ckw, pkw, nchains=70, record_accept=1, scam_fast=1)
     e.init(); e.run(9)
     cfg = oracle.make_cfg(**ckw); prob = oracle.Problem(**pkw)
-    th = e.theta()
-    for c in (0, 63, 69):
-        o = oracle.run_chain(cfg, prob, chain_id=c, upto=9)
-        np.testing.assert_array_equal(e.accepted(c), o.accepted)
-        assert e.rng(c)[0] == o.rng_n
-        assert np.max(np.abs(th[c] - o.theta)) < 1e-9 * np.max(np.abs(o.theta))
+    assert e.last_kernel() == ("scam_mw_kernel<8>" if lanes else "scam_pooled_kernel<per-chain>"), e.last_kernel()
+    th, acc = e.theta(), _accepted_all(e, 70)[:, :9]
+    rng = [e.rng(c)[0] for c in range(70)]
     e.close()
+    os_ = _fast_oracle(oracle, "c5", cfg, prob, 0, 70, upto=9)
+    bad = [c for c, o in enumerate(os_) if not (np.array_equal(acc[c], o.accepted) and rng[c] == o.rng_n and np.array_equal(_bits(th[c]), _bits(o.theta)))]
+    assert not bad, "chains whose accept sequence, stream position or state is not the fast oracle's: %s" % bad[:12]
 
 
 @pytest.mark.parametrize("d,N", [(30, 200), (130, 150)])
@@ -112,7 +139,7 @@ def test_fast_pooled_scam_against_the_reference_order_form(oracle, d, N):
 
 def test_fast_scam_with_host_callbacks_equals_the_device_target(oracle):
     """The host-callback form of a SCAM sub-step (host_phase_kernel<5>) takes the same fast proposal: bit-equal to the
-    device-resident fast run."""
+    device-resident fast run, and both to the fast oracle."""
     from mcmcf90_amd import Engine, make_config, engine_from_problem
     z, cfg, prob = load("s1_gauss6_scam", oracle)
     ckw, pkw = _kw(z)
@@ -122,13 +149,19 @@ def test_fast_scam_with_host_callbacks_equals_the_device_target(oracle):
     L.mcxo_ssfun.restype = C.c_double
     dp = C.POINTER(C.c_double)
     npar = int(pkw["npar"])
-    e = Engine(make_config(npar, 3, chain_id0=5, scam_fast=1, **ckw))
+    e = Engine(make_config(npar, 3, chain_id0=5, scam_fast=1, record_accept=1, **ckw))
     e.setpar0(pkw["par0"]); e.setcmat0(np.asarray(pkw["cmat0"], dtype=float).reshape(npar, npar))
     e.setsigma2nobs(1.0, 1)
     e.set_target_host(lambda th: L.mcxo_ssfun(C.byref(tgt), th.ctypes.data_as(dp)))
     e.init(); e.run()
-    r = engine_from_problem(ckw, pkw, nchains=3, chain_id0=5, scam_fast=1)
+    r = engine_from_problem(ckw, pkw, nchains=3, chain_id0=5, scam_fast=1, record_accept=1)
     r.init(); r.run()
     np.testing.assert_array_equal(_bits(e.theta()), _bits(r.theta()))
     assert [e.rng(c)[0] for c in range(3)] == [r.rng(c)[0] for c in range(3)]
+    for c in range(3):
+        o = oracle.run_chain(oracle.make_cfg(**ckw), prob, chain_id=5 + c, scam_fast=True)
+        for g in (e, r):
+            np.testing.assert_array_equal(_bits(g.theta()[c]), _bits(o.theta))
+            np.testing.assert_array_equal(g.accepted(c), o.accepted)
+            assert g.rng(c)[0] == o.rng_n
     e.close(); r.close()
