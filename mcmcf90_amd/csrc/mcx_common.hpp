@@ -81,6 +81,18 @@ struct EngineDev {
 
 #define TIDX(base, tile, K, k, lane) ((base)[((size_t)(tile) * (size_t)(K) + (size_t)(k)) * 64 + (lane)])
 
+// What MCMC_savechain (MCMC_aux.F90:167-185) records of iteration `it` beside the accepted row, nycol = 1: the tile's accept ballot in
+// the ring's slot, each chain's sigma2 in the s2 ring where it is kept, and the ballot in the whole-run accept mask.
+MCX_DEV void record_iteration(const EngineDev &E, int tile, int lane, int it, unsigned long long ballot, double sigma2)
+{
+    const int slot = it % E.wcap;
+    if (E.hist) {
+        if (lane == 0) E.wacc[(size_t)tile * E.wcap + slot] = ballot;
+        if (E.record_s2) E.s2hist[((size_t)tile * E.wcap + slot) * 64 + lane] = sigma2;
+    }
+    if (E.accmask && lane == 0) E.accmask[(size_t)(it - 1) * E.ntiles + tile] = ballot;
+}
+
 // Packed upper triangle, ROW-major: element (i,j), i <= j, sits at rowstart(i) + (j - i).
 // Every sweep of the factor (proposal, update, downdate) walks whole rows, forwards or backwards,
 // so a tile's factor is one sequential HBM stream of 512-byte wave segments.

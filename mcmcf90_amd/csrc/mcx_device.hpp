@@ -354,4 +354,41 @@ MCX_DEV double d_alpha(double ss1, double pri1, double ss2, double pri2, double 
 
 MCX_DEV double min1(double x) { return (1.0 < x) ? 1.0 : x; }
 
+// MCMC_reject, MCMC_DRAM.F90:140-155: alpha >= 1 accepts without a draw, alpha <= 0 and a NaN alpha reject without one, anything
+// between draws ONE uniform and accepts on u <= alpha.  THE Metropolis decision of the lane-per-chain kernels.
+MCX_DEV bool mcmc_reject(double alpha, Rng &g)
+{
+    bool reject = true;
+    if (alpha >= 1.0) reject = false;
+    else if (alpha > 0.0) { double u = rng_uniform(g); if (u <= alpha) reject = false; }
+    return reject;
+}
+
+// The scalar part of MCMC_DR_alpha13, MCMC_DRAM.F90:162-186 (nycol = 1), the second-stage acceptance probability: 1 = where the chain
+// is, 2 = the rejected first-stage candidate, 3 = the second-stage candidate; qa = dx' iC dx with dx = 3 - 2, qb with dx = 1 - 2 (:180-182;
+// every kernel has its own quadratic forms).  alpha12 == 0 takes alpha32 = 0 without an exponential.
+MCX_DEV double dr_alpha13(double ss1, double pri1, double ss2, double pri2, double ss3, double pri3, double sigma2, double alpha12,
+                          double qa, double qb)
+{
+    double alpha32;
+    if (alpha12 == 0.0) alpha32 = 0.0;
+    else alpha32 = min1(d_exp(-0.5 * ((ss2 - ss3) / sigma2 + (pri2 - pri3))));
+    double l2 = -0.5 * ((ss3 - ss1) / sigma2 + (pri3 - pri1));
+    double q1 = -0.5 * (qa - qb);
+    return min1(d_exp(l2 + q1) * (1.0 - alpha32) / (1.0 - alpha12));
+}
+
+// Early rejection of an in-bounds candidate, MCMC_run_er.F90:60-89: the threshold's uniform is ALWAYS drawn (MCMC_sscrit,
+// MCMC_DRAM.F90:124-135); a prior at or above the threshold rejects before ss is looked at (counted in erstayed); else the threshold
+// is rescaled to the sum of squares and ss2 >= sscrit rejects.
+MCX_DEV bool er_reject(double ss1, double pri1, double ss2, double pri2, double sigma2, Rng &g, uint32_t &erstayed)
+{
+    bool reject;
+    double u = rng_uniform(g);
+    double sscrit = -2.0 * d_log(u) + ss1 / sigma2 + pri1;
+    if (pri2 >= sscrit) { reject = true; erstayed += 1; }
+    else { sscrit = sigma2 * (sscrit - pri2); reject = (ss2 >= sscrit); }
+    return reject;
+}
+
 } // namespace mcx

@@ -158,9 +158,7 @@ MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, con
             if (E.method != M_RAM) L.alpha12 = 0.0;
         } else {
             L.alpha12 = ny > 1 ? d_alpha_cols(ssv, L.pri1, sshev, pri2, s2v, ny, lane) : d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-            reject = true;
-            if (L.alpha12 >= 1.0) reject = false;
-            else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
+            reject = mcmc_reject(L.alpha12, L.g);
         }
         if (E.dodr) {
             const bool m = reject;
@@ -199,9 +197,7 @@ MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, con
         if (!inb) { L.bnd += 1; L.alpha12 = 0.0; reject = true; }
         else {
             L.alpha12 = ny > 1 ? d_alpha_cols(ssv, L.pri1, sshev, pri2, s2v, ny, lane) : d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-            reject = true;
-            if (L.alpha12 >= 1.0) reject = false;
-            else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
+            reject = mcmc_reject(L.alpha12, L.g);
         }
         if (!reject) {
             for (int j = 0; j < (ny > 1 ? ny : 0); ++j) GV(ssv, j) = GV(sshev, j);
@@ -275,6 +271,7 @@ MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, con
             if (!inb2) L.bnd += 1;
             else {
                 const double pri3 = GV(hev, HE_PRI), ss3 = GV(hev, HE_SS);
+                // dr_alpha13's statement with nycol > 1's sums over the columns beside it, spelled out
                 double alpha32, l2;
                 if (ny > 1) {
                     if (L.alpha12 == 0.0) alpha32 = 0.0;
@@ -293,9 +290,7 @@ MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, con
                 double qb = siC ? quadform_sym_shared(siC, lane, d, Xq, Yq) : quadform_sym(iCt, lane, d, Xq, Yq);
                 double q1 = -0.5 * (qa - qb);
                 double alpha13 = min1(d_exp(l2 + q1) * (1.0 - alpha32) / (1.0 - L.alpha12));
-                bool rej2 = true;
-                if (alpha13 >= 1.0) rej2 = false;
-                else if (alpha13 > 0.0) { double u = rng_uniform(L.g); if (u <= alpha13) rej2 = false; }
+                bool rej2 = mcmc_reject(alpha13, L.g);
                 if (!rej2) { L.dracc += 1; reject = false; dr_moved = true; ss2 = ss3; pri2 = pri3; }
             }
         }
@@ -413,6 +408,7 @@ __global__ __launch_bounds__(64) void run1_kernel(EngineDev E, double *r1, int d
         double alpha;
         if (drstage > 1 && E.dodr) {                      // MCMC_DR_alpha13, MCMC_DRAM.F90:162-186: 1 = oldpar2, 2 = oldpar1, 3 = newpar
             const double pri2c = GV(sc, R1_PRI2), alpha12 = GV(sc, R1_A12);
+            // dr_alpha13's statement with nycol > 1's sums over the columns beside it, spelled out
             double alpha32, l2;
             if (ny > 1) {
                 if (alpha12 == 0.0) alpha32 = 0.0;
@@ -434,9 +430,7 @@ __global__ __launch_bounds__(64) void run1_kernel(EngineDev E, double *r1, int d
         } else {
             alpha = ny > 1 ? d_alpha_cols(ssp1, pri1, ssn, pri, s2v, ny, lane) : d_alpha(GV(ssp1, 0), pri1, GV(ssn, 0), pri, L.sigma2);
         }
-        bool reject = true;                               // MCMC_reject, MCMC_DRAM.F90:140-155
-        if (alpha >= 1.0) reject = false;
-        else if (alpha > 0.0) { double u = rng_uniform(L.g); if (u <= alpha) reject = false; }
+        const bool reject = mcmc_reject(alpha, L.g);
         GV(sc, R1_ALPHA) = alpha; GV(sc, R1_REJECT) = reject ? 1.0 : 0.0;
     } else if (MODE == 1 || MODE == 2) {
         gen_normals(L.g, zs_t, lane, d, true);

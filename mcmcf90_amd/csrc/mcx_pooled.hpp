@@ -193,19 +193,12 @@ __global__ __launch_bounds__(64, (!DR && W2) ? 2 : 1) void pooled_mfma_kernel(En
         bool reject;
         if (!DR && E.method == M_ER) {                    // early rejection, MCMC_run_er.F90:60-89 (no second stage with it)
             if (!inb) { L.bnd += 1; reject = true; }
-            else {
-                double u = rng_uniform(L.g);              // MCMC_sscrit, MCMC_DRAM.F90:124-135: always drawn
-                double sscrit = -2.0 * d_log(u) + L.ss1 / L.sigma2 + L.pri1;
-                if (pri2 >= sscrit) { reject = true; erstayed += 1; }
-                else { sscrit = L.sigma2 * (sscrit - pri2); reject = (ss2 >= sscrit); }
-            }
+            else reject = er_reject(L.ss1, L.pri1, ss2, pri2, L.sigma2, L.g, erstayed);
         }
         else if (!inb) { if (!DR) L.bnd += 1; reject = true; L.alpha12 = 0.0; }
         else {
             L.alpha12 = d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-            reject = true;
-            if (L.alpha12 >= 1.0) reject = false;
-            else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
+            reject = mcmc_reject(L.alpha12, L.g);
         }
         // ---- second stage: one delayed-rejection try with R2 = R/drscale (MCMC_run.F90:65-91)
         bool dr_moved = false;
@@ -234,16 +227,8 @@ __global__ __launch_bounds__(64, (!DR && W2) ? 2 : 1) void pooled_mfma_kernel(En
             if (m) {
                 if (!inb2) L.bnd += 1;
                 else {
-                    // MCMC_DR_alpha13, MCMC_DRAM.F90:162-186
-                    double alpha32;
-                    if (L.alpha12 == 0.0) alpha32 = 0.0;
-                    else alpha32 = min1(d_exp(-0.5 * ((ss2 - ss3) / L.sigma2 + (pri2 - pri3))));
-                    const double l2 = -0.5 * ((ss3 - L.ss1) / L.sigma2 + (pri3 - L.pri1));
-                    const double q1 = -0.5 * (qf[0] - qf[1]);
-                    const double alpha13 = min1(d_exp(l2 + q1) * (1.0 - alpha32) / (1.0 - L.alpha12));
-                    bool rej2 = true;
-                    if (alpha13 >= 1.0) rej2 = false;
-                    else if (alpha13 > 0.0) { double u = rng_uniform(L.g); if (u <= alpha13) rej2 = false; }
+                    const double alpha13 = dr_alpha13(L.ss1, L.pri1, ss2, pri2, ss3, pri3, L.sigma2, L.alpha12, qf[0], qf[1]);
+                    bool rej2 = mcmc_reject(alpha13, L.g);
                     if (!rej2) { L.dracc += 1; reject = false; dr_moved = true; ss2 = ss3; pri2 = pri3; }
                 }
             }
@@ -262,11 +247,7 @@ __global__ __launch_bounds__(64, (!DR && W2) ? 2 : 1) void pooled_mfma_kernel(En
             copy_vec_wide<MCX_POOLED_CB>(theta_t, dr_moved ? c2_t : cand_t, h, lane, d);   // newpar = newpar2 when the DR try was accepted
             if (h) GV(h, d) = L.ss1;
         }
-        if (E.hist) {
-            if (lane == 0) E.wacc[(size_t)tile * E.wcap + slot] = ballot;
-            if (E.record_s2) E.s2hist[((size_t)tile * E.wcap + slot) * 64 + lane] = L.sigma2;
-        }
-        if (E.accmask && lane == 0) E.accmask[(size_t)(it - 1) * E.ntiles + tile] = ballot;
+        record_iteration(E, tile, lane, it, ballot, L.sigma2);
         PH(6)
     }
     lane_store(E, tile, lane, L);

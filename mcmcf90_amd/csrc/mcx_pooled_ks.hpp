@@ -274,19 +274,12 @@ __global__ __launch_bounds__(64, 2) void pooled_mfma_ks_kernel(EngineDev E, int 
         bool reject;
         if (E.method == M_ER) {                           // early rejection, MCMC_run_er.F90:60-89
             if (!inb) { L.bnd += 1; reject = true; }
-            else {
-                double u = rng_uniform(L.g);              // MCMC_sscrit, MCMC_DRAM.F90:124-135: always drawn
-                double sscrit = -2.0 * d_log(u) + L.ss1 / L.sigma2 + L.pri1;
-                if (pri2 >= sscrit) { reject = true; erstayed += 1; }
-                else { sscrit = L.sigma2 * (sscrit - pri2); reject = (ss2 >= sscrit); }
-            }
+            else reject = er_reject(L.ss1, L.pri1, ss2, pri2, L.sigma2, L.g, erstayed);
         }
         else if (!inb) { L.bnd += 1; reject = true; L.alpha12 = 0.0; }
         else {
             L.alpha12 = d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-            reject = true;
-            if (L.alpha12 >= 1.0) reject = false;
-            else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
+            reject = mcmc_reject(L.alpha12, L.g);
         }
         PHK(5)
         if (reject) { L.stayed += 1; L.curcount += 1; }
@@ -302,11 +295,7 @@ __global__ __launch_bounds__(64, 2) void pooled_mfma_ks_kernel(EngineDev E, int 
             copy_vec_wide<MCX_POOLED_CB>(theta_t, cand_t, h, lane, d);
             if (h) GV(h, d) = L.ss1;
         }
-        if (E.hist) {
-            if (lane == 0) E.wacc[(size_t)tile * E.wcap + slot] = ballot;
-            if (E.record_s2) E.s2hist[((size_t)tile * E.wcap + slot) * 64 + lane] = L.sigma2;
-        }
-        if (E.accmask && lane == 0) E.accmask[(size_t)(it - 1) * E.ntiles + tile] = ballot;
+        record_iteration(E, tile, lane, it, ballot, L.sigma2);
         PHK(6)
     }
     lane_store(E, tile, lane, L);

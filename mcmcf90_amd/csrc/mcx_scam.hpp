@@ -100,9 +100,7 @@ __global__ __launch_bounds__(64, MCX_SCAM_WAVES) void scam_kernel(EngineDev E, i
             if (!inb) { L.bnd += 1; L.alpha12 = 0.0; reject = true; }
             else {
                 L.alpha12 = d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-                reject = true;
-                if (L.alpha12 >= 1.0) reject = false;
-                else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
+                reject = mcmc_reject(L.alpha12, L.g);
             }
             if (!reject) {
                 L.ss1 = ss2; L.pri1 = pri2; rejall = false;
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(64, MCX_SCAM_WAVES) void scam_kernel(EngineDev E, i
         }
         unsigned long long ballot = __ballot(!rejall);
         const int slot = it % E.wcap;
-        if (E.hist) {
+        if (E.hist) {                                   // one test for the row and for record_iteration's statement, spelled out
             if (!rejall) {
                 double *h = E.hist + ((size_t)tile * E.wcap + slot) * (size_t)E.hs * 64;
                 for (int k = 0; k < d; ++k) GV(h, k) = GV(theta_t, k);
@@ -191,7 +189,7 @@ __global__ __launch_bounds__(64 * NW) void scam_mw_kernel(EngineDev E, int it0, 
                 if (!inb) { L.bnd += 1; L.alpha12 = 0.0; reject = true; }
                 else {
                     L.alpha12 = d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-                    reject = true;
+                    reject = true;                              // mcmc_reject's statement, spelled out: DESIGN.md section 4
                     if (L.alpha12 >= 1.0) reject = false;
                     else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
                 }
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(64 * NW) void scam_mw_kernel(EngineDev E, int it0, 
             }
             unsigned long long ballot = __ballot(!rejall);
             const int slot = it % E.wcap;
-            if (E.hist) {
+            if (E.hist) {                               // one test for the row and for record_iteration's statement, spelled out
                 if (!rejall) {
                     double *h = E.hist + ((size_t)tile * E.wcap + slot) * (size_t)E.hs * 64;
                     copy_vec(h, theta_t, nullptr, lane, d);
@@ -471,7 +469,7 @@ MCX_DEV void scam_pooled_body(const EngineDev &E, int it0, int it1, double *X, i
                 if (!inb) { L.bnd += 1; L.alpha12 = 0.0; reject = true; }
                 else {
                     L.alpha12 = d_alpha(L.ss1, L.pri1, ss2, pri2, L.sigma2);
-                    reject = true;
+                    reject = true;                              // mcmc_reject's statement, spelled out: DESIGN.md section 4
                     if (L.alpha12 >= 1.0) reject = false;
                     else if (L.alpha12 > 0.0) { double u = rng_uniform(L.g); if (u <= L.alpha12) reject = false; }
                 }
@@ -506,7 +504,7 @@ MCX_DEV void scam_pooled_body(const EngineDev &E, int it0, int it1, double *X, i
             }
             unsigned long long ballot = __ballot(!rejall);
             const int slot = it % E.wcap;
-            if (E.hist) {
+            if (E.hist) {                               // one test for the row and for record_iteration's statement, spelled out
                 if (!rejall) {
                     double *h = E.hist + ((size_t)tile * E.wcap + slot) * (size_t)E.hs * 64;
                     for (int k = 0; k < d; ++k) GV(h, k) = GV(theta_t, k);

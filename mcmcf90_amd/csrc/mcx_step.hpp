@@ -511,21 +511,14 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
         bool reject;
         if (!RAM && !DR && E.method == M_ER) {            // early rejection, MCMC_run_er.F90:60-89
             if (!inb) { bnd += 1; reject = true; }
-            else {
-                double u = rng_uniform(g);                // MCMC_sscrit, MCMC_DRAM.F90:124-135: always drawn
-                double sscrit = -2.0 * d_log(u) + ss1 / sigma2 + pri1;
-                if (pri2 >= sscrit) { reject = true; erstayed += 1; }
-                else { sscrit = sigma2 * (sscrit - pri2); reject = (ss2 >= sscrit); }
-            }
+            else reject = er_reject(ss1, pri1, ss2, pri2, sigma2, g, erstayed);
         } else if (!inb) {
             if (!DR) bnd += 1;                            // MCMC_run.F90:49
             reject = true;
             if (!RAM) alpha12 = 0.0;                      // RAM leaves alpha12 stale: MCMC_run_ram.F90:52-54
         } else {
             alpha12 = d_alpha(ss1, pri1, ss2, pri2, sigma2);
-            reject = true;                                // MCMC_reject, MCMC_DRAM.F90:140-155
-            if (alpha12 >= 1.0) reject = false;
-            else if (alpha12 > 0.0) { double u = rng_uniform(g); if (u <= alpha12) reject = false; }
+            reject = mcmc_reject(alpha12, g);
         }
         // ---- second stage: one delayed-rejection try with R2 = R/drscale (MCMC_run.F90:65-91)
         bool dr_moved = false;
@@ -547,7 +540,7 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
                 else {
                     double pri3 = target_prior(E.tgt, d, lane, c2_t);
                     double ss3 = target_ss<false>(E.tgt, d, lane, c2_t, g_mu, g_lamT);
-                    // MCMC_DR_alpha13, MCMC_DRAM.F90:162-186
+                    // dr_alpha13's statement, spelled out: the quadratic forms run between l2 and q1
                     double alpha32;
                     if (alpha12 == 0.0) alpha32 = 0.0;
                     else alpha32 = min1(d_exp(-0.5 * ((ss2 - ss3) / sigma2 + (pri2 - pri3))));
@@ -559,9 +552,7 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
                     double qb = POOLED ? quadform_sym_shared(g_sharediC, lane, d, X, Y) : quadform_sym(iCt, lane, d, X, Y);
                     double q1 = -0.5 * (qa - qb);
                     double alpha13 = min1(d_exp(l2 + q1) * (1.0 - alpha32) / (1.0 - alpha12));
-                    bool rej2 = true;
-                    if (alpha13 >= 1.0) rej2 = false;
-                    else if (alpha13 > 0.0) { double u = rng_uniform(g); if (u <= alpha13) rej2 = false; }
+                    bool rej2 = mcmc_reject(alpha13, g);
                     if (!rej2) { dracc += 1; reject = false; dr_moved = true; ss2 = ss3; pri2 = pri3; }
                 }
             }
@@ -582,11 +573,7 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
             copy_vec(theta_t, src, h, lane, d);
             if (h) GV(h, d) = ss1;
         }
-        if (E.hist) {
-            if (lane == 0) E.wacc[(size_t)tile * E.wcap + slot] = ballot;
-            if (E.record_s2) E.s2hist[((size_t)tile * E.wcap + slot) * 64 + lane] = sigma2;
-        }
-        if (E.accmask && lane == 0) E.accmask[(size_t)(it - 1) * E.ntiles + tile] = ballot;
+        record_iteration(E, tile, lane, it, ballot, sigma2);
         // ---- the next iteration's normals: nothing else draws between here and its MCMC_propose
         const bool pre = (it < it1);
         if (pre) su_n = gen_normals<RAM ? 1 : MCX_RNG_NB>(g, zn_t, lane, d, true);
@@ -744,9 +731,7 @@ MCX_DEV void dr_body(const EngineDev &E, int it0, int it1, const double *__restr
         if (!inb) { reject = true; alpha12 = 0.0; }         // (with DR an out-of-bounds first stage is not counted, MCMC_run.F90:49)
         else {
             alpha12 = d_alpha(ss1, pri1, ss2, pri2, sigma2);
-            reject = true;                                  // MCMC_reject, MCMC_DRAM.F90:140-155
-            if (alpha12 >= 1.0) reject = false;
-            else if (alpha12 > 0.0) { double u = rng_uniform(g); if (u <= alpha12) reject = false; }
+            reject = mcmc_reject(alpha12, g);
         }
         // ---- second stage: one delayed-rejection try with R2 = R/drscale (MCMC_run.F90:65-91)
         bool dr_moved = false;
@@ -762,7 +747,7 @@ MCX_DEV void dr_body(const EngineDev &E, int it0, int it1, const double *__restr
                 else {
                     double pri3 = target_prior(E.tgt, d, lane, c2_t);
                     double ss3 = target_ss<false>(E.tgt, d, lane, c2_t, g_mu, g_lamT);
-                    // MCMC_DR_alpha13, MCMC_DRAM.F90:162-186
+                    // dr_alpha13's statement, spelled out: the quadratic forms run between l2 and q1
                     double alpha32;
                     if (alpha12 == 0.0) alpha32 = 0.0;
                     else alpha32 = min1(d_exp(-0.5 * ((ss2 - ss3) / sigma2 + (pri2 - pri3))));
@@ -782,9 +767,7 @@ MCX_DEV void dr_body(const EngineDev &E, int it0, int it1, const double *__restr
                     quadform2_panels(E.iC + (size_t)tile * E.P * 64, lane, d, zb_t, cand_t, ysa_t, ysb_t, qa, qb);
                     double q1 = -0.5 * (qa - qb);
                     double alpha13 = min1(d_exp(l2 + q1) * (1.0 - alpha32) / (1.0 - alpha12));
-                    bool rej2 = true;
-                    if (alpha13 >= 1.0) rej2 = false;
-                    else if (alpha13 > 0.0) { double u = rng_uniform(g); if (u <= alpha13) rej2 = false; }
+                    bool rej2 = mcmc_reject(alpha13, g);
                     if (!rej2) { dracc += 1; reject = false; dr_moved = true; ss2 = ss3; pri2 = pri3; }
                 }
             }
@@ -805,11 +788,7 @@ MCX_DEV void dr_body(const EngineDev &E, int it0, int it1, const double *__restr
             else copy_vec(theta_t, cand_t, h, lane, d);            // that is global or LDS by the lane would mean FLAT accesses)
             if (h) GV(h, d) = ss1;
         }
-        if (E.hist) {
-            if (lane == 0) E.wacc[(size_t)tile * E.wcap + slot] = ballot;
-            if (E.record_s2) E.s2hist[((size_t)tile * E.wcap + slot) * 64 + lane] = sigma2;
-        }
-        if (E.accmask && lane == 0) E.accmask[(size_t)(it - 1) * E.ntiles + tile] = ballot;
+        record_iteration(E, tile, lane, it, ballot, sigma2);
     }
 
     TIDX(E.rngn, tile, 1, 0, lane) = g.n;
