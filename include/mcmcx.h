@@ -303,6 +303,43 @@ int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxl
 /* the finish: stats vector (one engine's, or the sum of several) -> table[nfields][8] (no counterpart in the reference) */
 int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, double *table);
 
+/* ---- the summary of an elementwise function of the retained samples (no counterpart in the reference): the other half of the standard
+ * table -- tail ESS, folded split-R-hat, the MCSE of the sd, the ESS at a quantile -- is the summary above of u(x) instead of x, reduced
+ * where the ring lies, with the same scratch (plus nfields doubles for a) and without a copy of the window.  The definition, restated
+ * bit for bit in numpy by tests/diag_xf_ref.py:
+ *   For a call with `kind` and a per-field parameter a[nfields] the stats vector is BY DEFINITION the vector mcmcx_samples_stats would
+ *   return if every stored value x of field f were replaced by u_f(x):
+ *     kind 0, MCMCX_XF_IDENTITY:  u_f(x) = x.  a is not looked at and may be NULL; the result has the same bits as mcmcx_samples_stats.
+ *     kind 1, MCMCX_XF_LE:        u_f(x) = 1.0 if key(x) <= key(a_f), else +0.0 -- the KEY order of mcmcx_samples_order_stats below, not
+ *                                 the IEEE comparison: le of mcmcx_samples_counts and the values of mcmcx_samples_quantiles mean the
+ *                                 same thing here, NaNs take part and -0.0 lies below +0.0.
+ *     kind 2, MCMCX_XF_FOLD:      u_f(x) = fabs(x - a_f): one IEEE subtraction, then the sign cleared.
+ *     kind 3, MCMCX_XF_SQUARE:    d = x - a_f;  u_f(x) = d * d: two IEEE operations, no contraction.
+ *   Everything after u is the summary's definition above, word for word: y_i = u(x_i) - shift_f, the half means, the lag sums in their
+ *   order, the tile tree with padding lanes masked to +0.0, the tiles' pairwise tree, the vector's length and layout.  shift == NULL
+ *   means u_f of field f of chain 0 in window sample 0.  mcmcx_samples_diag finishes the vector unchanged, and it stays additive over
+ *   engines that used the same kind, a and shift.
+ *   Non-finite values propagate as the arithmetic says (kind 1 maps every value, NaNs included, to 1.0 or +0.0).  An indicator that is
+ *   constant over the window -- a_f below or above every value -- has G_0 = 0, so W = 0 and its R-hat and ESS are NaN (0 / 0), not 1.
+ * Reading the numbers: tail ESS is the smaller ess of kind 1 at the 5 % and the 95 % quantile; the MCSE of P(x <= q) is
+ * sqrt(p (1 - p) / ess).  Folded split-R-hat is rhat of kind 2 at the median: all chains start at par0, so the plain R-hat measures
+ * drift, and chains that agree in location but differ in scale show only here.  The MCSE of the sd is mcse / (2 sd) of kind 3 at the
+ * mean (the delta method on the variance).  For an indicator a shift of zeros is exact (every y is 0 or 1).
+ * a and shift are host memory in both forms and are staged during the call.  mcmcx_samples_stats_of copies the vector to host memory
+ * and synchronises; mcmcx_samples_stats_of_dev writes it into the caller's DEVICE buffer, asynchronous on the engine's stream.  Refused
+ * with -53 (the reason in mcmcx_last_error) on the host, before anything is launched or allocated: a kind outside 0 .. 3, a NULL a with
+ * kind != 0, and everything mcmcx_samples_stats refuses. */
+#define MCMCX_XF_IDENTITY 0
+#define MCMCX_XF_LE 1
+#define MCMCX_XF_FOLD 2
+#define MCMCX_XF_SQUARE 3
+/* the stats vector of u(window) to host memory (no counterpart in the reference) */
+int mcmcx_samples_stats_of(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t kind, const double *a /* [nfields] host */,
+                           const double *shift /* [nfields] host, or NULL */, double *host_out);
+/* ... into a device buffer, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_stats_of_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t kind, const double *a,
+                               const double *shift, void *dev_out);
+
 /* ---- exact order statistics, tail counts and quantiles of the retained samples, reduced on the device where the ring lies (no
  * counterpart in the reference): credible intervals, medians and tail probabilities of every field without moving the window.  The
  * r-th smallest of a multiset and an integer count depend on no order of summation, so the results are exact; the definition is
@@ -526,6 +563,14 @@ int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, in
  * the arguments decide before a device is looked for. */
 int mcmcx_debug_samples_hist(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t nbins,
                              const double *edges, int32_t npairs, const int32_t *pairs, int32_t chunk, int64_t *out1, int64_t *out2);
+/* The summary's own kernels, of u(x), on a caller's array (no counterpart in the reference; tests only): values[ns][nfields][nchains]
+ * host is laid out as a store of ns slots and ceil(nchains / 64) tiles, the padding lanes of the last tile filled with NaN by this
+ * entry (a kernel that did not mask them would sum them, and count them under kind 1 with a NaN a); out takes the stats vector of
+ * mcmcx_samples_stats_of.  A run cannot put +-0, +-inf, NaNs, denormals or values equal to a into the ring; this can.  a: [nfields]
+ * host (NULL with kind 0), shift: [nfields] host or NULL.  Refusals are -53, what the arguments decide before a device is looked for:
+ * a kind outside 0 .. 3, a NULL a with kind != 0, a null values or out, nchains or nfields < 1, ns < 4, maxlag out of range. */
+int mcmcx_debug_samples_stats(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t maxlag,
+                              int32_t kind, const double *a, const double *shift, double *out);
 /* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
  * inverse != 0 the bits whose key x's bits are.  Needs no device. */
 int64_t mcmcx_debug_quant_key(double x, int32_t inverse);

@@ -142,6 +142,10 @@ SYMBOLS["mcmcx_samples_hist_edges"] = (C.c_int, [C.c_double, C.c_double, C.c_int
 SYMBOLS["mcmcx_samples_hist_density"] = (C.c_int, [_LP, _DP, C.c_int32, C.c_int32, _DP])
 SYMBOLS["mcmcx_debug_samples_hist"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, _IP, C.c_int32,
                                                  _LP, _LP])
+# the summary of an elementwise function of the stored values (tail ESS, folded R-hat, MCSE of the sd)
+SYMBOLS["mcmcx_samples_stats_of"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP])
+SYMBOLS["mcmcx_samples_stats_of_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, C.c_void_p])
+SYMBOLS["mcmcx_debug_samples_stats"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP])
 
 _lib = None
 

@@ -1007,14 +1007,33 @@ int32_t mcmcx_samples_stats_len(mcmcx_handle h, int32_t maxlag)
 int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, void *dev_out)
 {
     int rc = diag_check(h, s0, ns, maxlag, dev_out, "mcmcx_samples_stats_dev"); if (rc) return rc;
-    return diag_engine(h, s0, ns, maxlag, shift, (double *)dev_out, nullptr);
+    return diag_engine(h, s0, ns, maxlag, XF_IDENTITY, nullptr, shift, (double *)dev_out, nullptr);
 }
 
 int mcmcx_samples_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, double *host_out)
 {
     int rc = diag_check(h, s0, ns, maxlag, host_out, "mcmcx_samples_stats"); if (rc) return rc;
     double *staged = nullptr;
-    if ((rc = diag_engine(h, s0, ns, maxlag, shift, nullptr, &staged))) return rc;
+    if ((rc = diag_engine(h, s0, ns, maxlag, XF_IDENTITY, nullptr, shift, nullptr, &staged))) return rc;
+    return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
+}
+
+// ... of an elementwise function of the stored values (mcx_diag_xf.hpp): kind 0 runs the summary's own kernels
+int mcmcx_samples_stats_of_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t kind, const double *a, const double *shift,
+                               void *dev_out)
+{
+    int rc = diag_xf_check(kind, a, "mcmcx_samples_stats_of_dev"); if (rc) return rc;
+    if ((rc = diag_check(h, s0, ns, maxlag, dev_out, "mcmcx_samples_stats_of_dev", -53))) return rc;
+    return diag_engine(h, s0, ns, maxlag, kind, a, shift, (double *)dev_out, nullptr);
+}
+
+int mcmcx_samples_stats_of(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t kind, const double *a, const double *shift,
+                           double *host_out)
+{
+    int rc = diag_xf_check(kind, a, "mcmcx_samples_stats_of"); if (rc) return rc;
+    if ((rc = diag_check(h, s0, ns, maxlag, host_out, "mcmcx_samples_stats_of", -53))) return rc;
+    double *staged = nullptr;
+    if ((rc = diag_engine(h, s0, ns, maxlag, kind, a, shift, nullptr, &staged))) return rc;
     return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
 }
 
@@ -1374,6 +1393,42 @@ int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, in
     int rc = cov_launch(W, w, shift, dout, 0); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(0));
     HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the summary's own kernels, of u(x), on a caller's array: a store of ns slots, ceil(nchains / 64) tiles and nfields fields filled from
+// values[ns][nfields][nchains]; the padding lanes of the last tile hold NaN, which a kernel that did not mask them would sum -- and under
+// kind 1 with a positive-NaN a count
+int mcmcx_debug_samples_stats(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t maxlag,
+                              int32_t kind, const double *a, const double *shift, double *out)
+{
+    const char *who = "mcmcx_debug_samples_stats";
+    int rc = diag_xf_check(kind, a, who); if (rc) return rc;
+    if (!values || !out) return fail(-53, std::string(who) + ": null argument");
+    if (nchains < 1 || nfields < 1 || ns < 4) return fail(-53, std::string(who) + ": nchains, nfields < 1 or ns < 4");
+    if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-53, std::string(who) + ": maxlag " + std::to_string(maxlag) +
+        " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const int T = (nchains + 63) / 64;
+    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
+    std::vector<double> host(words, std::nan(""));
+    for (int s = 0; s < ns; ++s)
+        for (int f = 0; f < nfields; ++f)
+            for (int c = 0; c < nchains; ++c)
+                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
+                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
+    const size_t need = diag_scratch_len(T, nfields, maxlag, kind), slen = (size_t)diag_stats_len(nfields, maxlag);
+    DevBufs g;
+    double *store = nullptr, *w = nullptr;
+    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, need * 8));
+    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
+    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
+    double *dout = w + need - slen;
+    if ((rc = diag_launch(W, w, maxlag, kind, a, shift, dout, 0))) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    HIPCHK(hipMemcpy(out, dout, slen * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

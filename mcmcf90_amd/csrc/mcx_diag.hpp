@@ -36,9 +36,11 @@ struct DiagArgs {
 // Samples j0 .. j0 + B - 1 of a half (those below n): z_j = (x_j - shift) - m enters the window at j % W and every lag sum takes its
 // product, a_t = a_t + z_{j-t} z_j -- g_t's terms in g_t's order (i = j - t ascending; the product commutes).  HEAD: the half's first
 // block, where lag t has no partner yet for j < t (decided at compile time: j = u there).  Rows are loaded DIAG_LB at a time, past the
-// half's end the last one again (a valid row, not used).
-template <int W, int B, bool HEAD, class Row>
-MCX_DEV void diag_block(Row &&row, int j0, int n, double sh, double m, double (&z)[W], double (&a)[W])
+// half's end the last one again (a valid row, not used).  xf: the elementwise function a value passes where it leaves its load -- the
+// summary's own is the identity, the transformed summaries' (mcx_diag_xf.hpp) are compile-time functors too.
+struct XfIdentity { MCX_DEV double operator()(double x) const { return x; } };
+template <int W, int B, bool HEAD, class Row, class U = XfIdentity>
+MCX_DEV void diag_block(Row &&row, int j0, int n, double sh, double m, double (&z)[W], double (&a)[W], const U &xf = U())
 {
 #pragma unroll
     for (int u0 = 0; u0 < B; u0 += DIAG_LB) {
@@ -50,7 +52,7 @@ MCX_DEV void diag_block(Row &&row, int j0, int n, double sh, double m, double (&
         for (int q = 0; q < DIAG_LB; ++q) {
             const int u = u0 + q;
             if (u < B && j0 + u < n) {
-                const double zn = (v[q] - sh) - m;
+                const double zn = (xf(v[q]) - sh) - m;
                 z[u % W] = zn;
 #pragma unroll
                 for (int t = 0; t < W; ++t)

@@ -42,5 +42,6 @@
 #include "mcx_samples.hpp"
 #include "mcx_diag.hpp"
 #include "mcx_quant.hpp"
+#include "mcx_diag_xf.hpp"
 #include "mcx_cov.hpp"
 #include "mcx_hist.hpp"

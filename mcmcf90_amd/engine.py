@@ -62,6 +62,7 @@ def sample_store_offset(slot, ntiles, nfields, tile, field):
 
 DIAG_MAXLAG = 32
 DIAG_COLUMNS = ("mean", "sd", "rhat", "ess", "mcse", "W", "Bn", "truncated")
+XF_IDENTITY, XF_LE, XF_FOLD, XF_SQUARE = 0, 1, 2, 3            # Engine.samples_stats_of's kinds (MCMCX_XF_*)
 
 
 def samples_stats_len(nfields, maxlag):
@@ -504,6 +505,31 @@ class Engine:
         return self._dev(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))),
                          lambda p: self.L.mcmcx_samples_stats_dev(self.h, int(s0), ns, int(maxlag), _dp(sh), p))
 
+    # --- the summary of an elementwise function of the retained samples (mcmcx_samples_stats_of)
+    def _stats_of_args(self, kind, a, s0, ns, shift, who):
+        """(ns, a, shift) of a transformed summary: a and shift as contiguous arrays of nfields values, or None"""
+        ns, _, _, nf = self._window(s0, ns)
+        av = None if a is None else _f64(a)
+        if av is not None and av.size != nf:
+            raise McmcError("%s: a has %d values, a sample has %d fields" % (who, av.size, nf))
+        return ns, av, self._shift(shift, nf, who)
+
+    def samples_stats_of(self, kind, a=None, s0=0, ns=None, maxlag=16, shift=None):
+        """The stats vector `samples_stats` would return if every stored value x of field f were u_f(x): kind XF_IDENTITY x (a is not
+        looked at), XF_LE 1.0 where key(x) <= key(a[f]) else 0.0 (the order of samples_counts' le), XF_FOLD |x - a[f]|,
+        XF_SQUARE (x - a[f])^2.  shift = None: u_f of chain 0 in window sample 0.  `samples_diag` finishes it; additive over engines
+        that were given the same kind, a and shift."""
+        ns, av, sh = self._stats_of_args(kind, a, s0, ns, shift, "samples_stats_of")
+        out = np.zeros(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))))
+        self._chk(self.L.mcmcx_samples_stats_of(self.h, int(s0), ns, int(maxlag), int(kind), _dp(av), _dp(sh), _dp(out)))
+        return out
+
+    def samples_stats_of_torch(self, kind, a=None, s0=0, ns=None, maxlag=16, shift=None):
+        """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        ns, av, sh = self._stats_of_args(kind, a, s0, ns, shift, "samples_stats_of_torch")
+        return self._dev(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))),
+                         lambda p: self.L.mcmcx_samples_stats_of_dev(self.h, int(s0), ns, int(maxlag), int(kind), _dp(av), _dp(sh), p))
+
     # --- exact order statistics, tail counts and quantiles of the retained samples (mcmcx_samples_order_stats)
     def samples_order_stats(self, ranks, s0=0, ns=None):
         """[nfields][nr]: the values whose keys are the ranks[k]-th smallest (0-based) among the ns x nchains values of each field in
@@ -540,10 +566,22 @@ class Engine:
         self._chk(self.L.mcmcx_samples_quantiles(self.h, int(s0), ns, int(p.size), _dp(p), _dp(a)))
         return a
 
-    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None):
+    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None, tail=False):
         """dict of arrays over the fields: mean, sd, rhat, ess, mcse, W, Bn, truncated; `fields` names the rows, `iterations` are the
         window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound.  With `probs` also the
-        keys `probs` and `quantiles` ([nfields][nq], samples_quantiles of the same window)."""
+        keys `probs` and `quantiles` ([nfields][nq], samples_quantiles of the same window).
+
+        tail=True adds the diagnostics of the intervals and of the sd, each a summary of an elementwise function of the samples
+        (samples_stats_of) at the same maxlag, with q05, q50, q95 from samples_quantiles of the same window:
+          ess_tail        the smaller ess of the indicators x <= q05 and x <= q95 (XF_LE, a shift of zeros); NaN if either is
+          truncated_tail  the larger of their two `truncated` flags
+          rhat_folded     rhat of |x - q50| (XF_FOLD): chains that agree in location and differ in scale show here, not in rhat
+          ess_sd, mcse_sd ess of (x - mean)^2 (XF_SQUARE at the table's mean), and its mcse / (2 sd): the delta method on the
+                          variance, sd = sqrt(var) so d sd = d var / (2 sd)
+          ess_quantiles   with `probs`, [nfields][nq]: the ess of the indicator x <= quantiles[f][q]; the MCSE of P(x <= q) is
+                          sqrt(p (1 - p) / ess)
+        An indicator that is constant over the window (a quantile at the window's extreme) gives NaN.  Cost on top of tail=False:
+        4 + nq summary passes over the window and one quantile call.  `shift` applies to the plain table only."""
         ns, oldest, thin, nf = self._window(s0, ns)
         table = samples_diag(self.samples_stats(s0, ns, maxlag, shift), nf, maxlag)
         out = {k: table[:, j].copy() for j, k in enumerate(DIAG_COLUMNS)}
@@ -552,6 +590,22 @@ class Engine:
         if probs is not None:
             out["probs"] = _f64(probs).ravel().copy()
             out["quantiles"] = self.samples_quantiles(out["probs"], s0, ns)
+        if tail:
+            def of(kind, a, sh=None):
+                return samples_diag(self.samples_stats_of(kind, a, s0, ns, maxlag, sh), nf, maxlag)
+            ESS, MCSE, RHAT, TRUNC = (DIAG_COLUMNS.index(k) for k in ("ess", "mcse", "rhat", "truncated"))
+            zero = np.zeros(nf)
+            q = self.samples_quantiles([0.05, 0.5, 0.95], s0, ns)
+            lo, hi = of(XF_LE, q[:, 0], zero), of(XF_LE, q[:, 2], zero)
+            out["ess_tail"] = np.minimum(lo[:, ESS], hi[:, ESS])
+            out["truncated_tail"] = np.maximum(lo[:, TRUNC], hi[:, TRUNC])
+            out["rhat_folded"] = of(XF_FOLD, q[:, 1])[:, RHAT].copy()
+            sq = of(XF_SQUARE, out["mean"])
+            out["ess_sd"] = sq[:, ESS].copy()
+            out["mcse_sd"] = sq[:, MCSE] / (2.0 * out["sd"])
+            if probs is not None:
+                qs = out["quantiles"]
+                out["ess_quantiles"] = np.stack([of(XF_LE, qs[:, k], zero)[:, ESS] for k in range(qs.shape[1])], axis=1)
         return out
 
     # --- marginal and pairwise joint histograms of the retained samples (mcmcx_samples_hist / _hist2)
