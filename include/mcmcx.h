@@ -256,7 +256,8 @@ int mcmcx_get_samples_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, in
 
 /* ---- convergence summary of the retained samples, reduced on the device where the ring lies (no counterpart in the reference):
  * posterior mean and standard deviation, split-R-hat, bulk ESS (Stan's multi-chain estimator over split chains with Geyer's initial
- * monotone sequence) and MCSE of every field of the store.  Device scratch is ntiles x nfields x (maxlag + 3) doubles (plus nfields
+ * monotone sequence, applied to the values as they are: the rank-normalised R-hat and bulk ESS, which mean something for a heavy-tailed
+ * field too, are mcmcx_samples_stats_step's below) and MCSE of every field of the store.  Device scratch is ntiles x nfields x (maxlag + 3) doubles (plus nfields
  * for the shift and one stats vector), not a copy of the window; no sampling kernel and no state of the run is touched, so a run
  * with a summary call in the middle is the same run.  The definition is the contract -- sums in a fixed order, restated bit for bit
  * in numpy by tests/diag_ref.py:
@@ -494,6 +495,49 @@ int mcmcx_samples_hist_edges(double lo, double hi, int32_t nbins, double *edges_
 int mcmcx_samples_hist_density(const int64_t *counts, const double *edges, int32_t nfields, int32_t nbins,
                                double *density_out /* [nfields][nbins] */);
 
+/* ---- the summary of a step function of the retained samples (no counterpart in the reference): the rank-normalised split-R-hat and
+ * bulk ESS of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021) -- the Rhat and ess_bulk columns of Stan and ArviZ --, the ESS of an
+ * interval probability P(a <= x < b) and of any binned functional are the summary above of
+ *     u_f(x) = table_f[cell_f(x)]
+ * reduced where the ring lies, with the same scratch (plus the staged edge keys and table) and without a copy of the window.  The
+ * definition, restated bit for bit in numpy by tests/diag_step_ref.py:
+ *   Edges: edges[nfields][nbins + 1], host memory, 1 <= nbins <= MCMCX_STEP_MAXBINS (512 cells), held to the rules of mcmcx_samples_hist:
+ *   within a field non-decreasing by key; equal neighbours and +-inf are allowed; a NaN or a decreasing edge is refused.
+ *   Table: table[nfields][nbins + 2] doubles, host memory.  Any bits are allowed; NaN and inf propagate as the arithmetic says.
+ *   The stats vector is BY DEFINITION the vector mcmcx_samples_stats would return if every stored value x of field f were replaced by
+ *   table[f][cell_f(x)], cell_f(x) being the histograms' cell: the number of edges e_i of field f with key(e_i) <= key(x), 0 .. nbins + 1.
+ *   NaNs take part and -0.0 lies below +0.0.
+ *   Everything after u is the summary's definition above, word for word: y_i = u(x_i) - shift_f, the half means, the lag sums in their
+ *   order, the tile tree with padding lanes masked to +0.0, the tiles' pairwise tree, the vector's length and layout.  shift == NULL
+ *   means u_f of field f of chain 0 in window sample 0.  mcmcx_samples_diag finishes the vector unchanged, and it stays additive over
+ *   engines that used the same edges, table and shift.
+ * Rank normalisation over cells: with the edges at order statistics of the window (mcmcx_samples_order_stats), the counts of
+ * mcmcx_samples_hist and the table of mcmcx_samples_rank_scores, every value is replaced by the normal score of the AVERAGE RANK OF ITS
+ * CELL -- ties are treated as the average-rank convention treats them, and 128 cells give the exact rank-normalised R-hat within 5e-4
+ * and its ESS within 2.5 %.  A field that is constant over the window falls into one cell: G_0 = 0, NaN.
+ * mcmcx_samples_rank_scores, per field, with n the sum of the field's nbins + 2 cells and before_b the sum of the cells below b, both in
+ * int64_t: a cell with count_b > 0 gets
+ *     p = ((double)(2 before_b + count_b + 1) * 0.5 - 0.375) / ((double)n + 0.25)
+ * -- its average 1-based rank r in Blom's form (r - 3/8) / (n + 1/4) -- and the score Phi^-1(p); an empty cell gets +0.0.  Phi^-1 is
+ * Wichura's algorithm AS241, routine PPND16 (Applied Statistics 37, 1988), operation by operation, without contraction.
+ * edges, table and shift are host memory in both forms and are staged during the call.  mcmcx_samples_stats_step copies the vector to
+ * host memory and synchronises; mcmcx_samples_stats_step_dev writes it into the caller's DEVICE buffer, asynchronous on the engine's
+ * stream.  Refused with -54 (the reason in mcmcx_last_error) on the host, before anything is launched or allocated -- first what the
+ * arguments alone decide: a null output, edges or table, nbins outside 1 .. MCMCX_STEP_MAXBINS, a NaN or decreasing edge; then
+ * everything mcmcx_samples_stats refuses. */
+#define MCMCX_STEP_MAXBINS 510
+/* the stats vector of table[cell(window)] to host memory (no counterpart in the reference) */
+int mcmcx_samples_stats_step(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t nbins,
+                             const double *edges /* [nfields][nbins + 1] host */, const double *table /* [nfields][nbins + 2] host */,
+                             const double *shift /* [nfields] host, or NULL */, double *host_out);
+/* ... into a device buffer, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_stats_step_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t nbins, const double *edges,
+                                 const double *table, const double *shift, void *dev_out);
+/* 1-D counts[nfields][nbins + 2] (one engine's, or the sum of several) -> scores_out[nfields][nbins + 2], the table of normal scores.
+ * Pure host, no handle, no device; refuses (-54) a null argument, nfields < 1, nbins outside 1 .. MCMCX_STEP_MAXBINS, a negative count,
+ * a field whose counts add up to less than 1 (or to more than 2**61) (no counterpart in the reference) */
+int mcmcx_samples_rank_scores(const int64_t *counts, int32_t nfields, int32_t nbins, double *scores_out);
+
 /* Pooled mode across several GPUs: at every adaptation tick the engine writes its local moment vector
  * (mcmcx_pooled_moments_len doubles) to dev_buf, synchronises its stream and calls fn(user); fn must sum dev_buf
  * over all ranks in place (an RCCL all-reduce) and return after the result is visible.  Without a hook the local
@@ -571,6 +615,14 @@ int mcmcx_debug_samples_hist(int32_t device, int32_t nchains, int32_t nfields, i
  * a kind outside 0 .. 3, a NULL a with kind != 0, a null values or out, nchains or nfields < 1, ns < 4, maxlag out of range. */
 int mcmcx_debug_samples_stats(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t maxlag,
                               int32_t kind, const double *a, const double *shift, double *out);
+/* The step summary's own kernels on a caller's array (no counterpart in the reference; tests only): values[ns][nfields][nchains] host
+ * laid out as mcmcx_debug_samples_stats lays it out, the padding lanes of the last tile filled with NaN by this entry (a kernel that did
+ * not mask them would look them up in the last cell and sum them); out takes the stats vector of mcmcx_samples_stats_step.  edges:
+ * [nfields][nbins + 1] host, table: [nfields][nbins + 2] host, shift: [nfields] host or NULL.  Refusals are -54, what the arguments
+ * decide before a device is looked for: a null out, edges, table or values, nbins out of range, a NaN or decreasing edge, nchains or
+ * nfields < 1, ns < 4, maxlag out of range. */
+int mcmcx_debug_samples_stats_step(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t maxlag,
+                                   int32_t nbins, const double *edges, const double *table, const double *shift, double *out);
 /* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
  * inverse != 0 the bits whose key x's bits are.  Needs no device. */
 int64_t mcmcx_debug_quant_key(double x, int32_t inverse);

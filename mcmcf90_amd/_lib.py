@@ -146,6 +146,12 @@ SYMBOLS["mcmcx_debug_samples_hist"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32
 SYMBOLS["mcmcx_samples_stats_of"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP])
 SYMBOLS["mcmcx_samples_stats_of_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, C.c_void_p])
 SYMBOLS["mcmcx_debug_samples_stats"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP])
+# the summary of a step function of the stored values (rank-normalised R-hat and bulk ESS) and its table of normal scores
+SYMBOLS["mcmcx_samples_stats_step"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP, _DP])
+SYMBOLS["mcmcx_samples_stats_step_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP, C.c_void_p])
+SYMBOLS["mcmcx_debug_samples_stats_step"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP,
+                                                        _DP])
+SYMBOLS["mcmcx_samples_rank_scores"] = (C.c_int, [_LP, C.c_int32, C.c_int32, _DP])
 
 _lib = None
 

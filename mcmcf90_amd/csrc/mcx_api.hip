@@ -30,6 +30,7 @@
 #include "mcx_host_diag.hpp"
 #include "mcx_host_quant.hpp"
 #include "mcx_host_hist.hpp"
+#include "mcx_host_diag_step.hpp"
 #include "mcx_host_cov.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
@@ -1037,6 +1038,33 @@ int mcmcx_samples_stats_of(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxla
     return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
 }
 
+// ... of a step function of the stored values, u_f(x) = table_f[cell_f(x)] (mcx_diag_step.hpp)
+int mcmcx_samples_stats_step_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t nbins, const double *edges,
+                                 const double *table, const double *shift, void *dev_out)
+{
+    int rc = diag_step_check(h, s0, ns, maxlag, nbins, edges, table, dev_out, "mcmcx_samples_stats_step_dev"); if (rc) return rc;
+    return diag_step_engine(h, s0, ns, maxlag, nbins, edges, table, shift, (double *)dev_out, nullptr);
+}
+
+int mcmcx_samples_stats_step(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t nbins, const double *edges,
+                             const double *table, const double *shift, double *host_out)
+{
+    int rc = diag_step_check(h, s0, ns, maxlag, nbins, edges, table, host_out, "mcmcx_samples_stats_step"); if (rc) return rc;
+    double *staged = nullptr;
+    if ((rc = diag_step_engine(h, s0, ns, maxlag, nbins, edges, table, shift, nullptr, &staged))) return rc;
+    return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
+}
+
+// the table of normal scores from 1-D histogram counts: pure host, no handle, no device
+int mcmcx_samples_rank_scores(const int64_t *counts, int32_t nfields, int32_t nbins, double *scores_out)
+{
+    if (!counts || !scores_out) return fail(-54, "mcmcx_samples_rank_scores: null argument");
+    if (nfields < 1) return fail(-54, "mcmcx_samples_rank_scores: nfields < 1");
+    if (nbins < 1 || nbins > MCMCX_STEP_MAXBINS) return fail(-54, "mcmcx_samples_rank_scores: " + std::to_string(nbins) +
+        " bins, outside 1 .. " + std::to_string(MCMCX_STEP_MAXBINS));
+    return step_rank_scores(counts, nfields, nbins, scores_out);
+}
+
 int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, double *table)
 {
     if (!stats || !table) return fail(-49, "mcmcx_samples_diag: null argument");
@@ -1427,6 +1455,42 @@ int mcmcx_debug_samples_stats(int32_t device, int32_t nchains, int32_t nfields, 
     const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
     double *dout = w + need - slen;
     if ((rc = diag_launch(W, w, maxlag, kind, a, shift, dout, 0))) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    HIPCHK(hipMemcpy(out, dout, slen * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the step summary's own kernels on a caller's array, laid out as mcmcx_debug_samples_stats lays it out: the padding lanes of the last
+// tile hold NaN, which a kernel that did not mask them would look up (the last cell) and sum
+int mcmcx_debug_samples_stats_step(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t maxlag,
+                                   int32_t nbins, const double *edges, const double *table, const double *shift, double *out)
+{
+    const char *who = "mcmcx_debug_samples_stats_step";
+    int rc = diag_step_check_args(nbins, edges, table, out, who); if (rc) return rc;
+    if (!values) return fail(-54, std::string(who) + ": null values");
+    if (nchains < 1 || nfields < 1 || ns < 4) return fail(-54, std::string(who) + ": nchains, nfields < 1 or ns < 4");
+    if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-54, std::string(who) + ": maxlag " + std::to_string(maxlag) +
+        " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
+    if ((rc = hist_check_edges(edges, nfields, nbins, who, -54))) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const int T = (nchains + 63) / 64;
+    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
+    std::vector<double> host(words, std::nan(""));
+    for (int s = 0; s < ns; ++s)
+        for (int f = 0; f < nfields; ++f)
+            for (int c = 0; c < nchains; ++c)
+                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
+                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
+    const size_t need = diag_step_scratch_len(T, nfields, maxlag, nbins), slen = (size_t)diag_stats_len(nfields, maxlag);
+    DevBufs g;
+    double *store = nullptr, *w = nullptr;
+    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, need * 8));
+    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
+    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
+    double *dout = w + need - slen;
+    if ((rc = diag_step_launch(W, w, maxlag, nbins, edges, table, shift, dout, 0))) return rc;
     HIPCHK(hipStreamSynchronize(0));
     HIPCHK(hipMemcpy(out, dout, slen * 8, hipMemcpyDeviceToHost));
     return 0;

@@ -23,17 +23,18 @@ static int hist_check_npairs(int npairs, const void *pairs, const char *who)
 }
 
 // ... the edges, edges[nrows][nbins + 1]: no NaN, non-decreasing by key within a row (equal neighbours and +-inf are allowed), ...
-static int hist_check_edges(const double *edges, int nrows, int nbins, const char *who)
+// (`code`: -52; -54 from the step summary's entries, which hold their edges to the same rules)
+static int hist_check_edges(const double *edges, int nrows, int nbins, const char *who, int code = -52)
 {
     for (int f = 0; f < nrows; ++f) {
         const double *e = edges + (size_t)f * (size_t)(nbins + 1);
         unsigned long long prev = 0ull;
         for (int i = 0; i <= nbins; ++i) {
-            if (e[i] != e[i]) return fail(-52, std::string(who) + ": edge " + std::to_string(i) + " of field " + std::to_string(f) +
+            if (e[i] != e[i]) return fail(code, std::string(who) + ": edge " + std::to_string(i) + " of field " + std::to_string(f) +
                 " is a NaN");
             unsigned long long b; memcpy(&b, e + i, 8);
             const unsigned long long k = quant_key(b);
-            if (i > 0 && k < prev) return fail(-52, std::string(who) + ": edges " + std::to_string(i - 1) + " and " + std::to_string(i) +
+            if (i > 0 && k < prev) return fail(code, std::string(who) + ": edges " + std::to_string(i - 1) + " and " + std::to_string(i) +
                 " of field " + std::to_string(f) + " decrease (the key order: -0.0 lies below +0.0)");
             prev = k;
         }

@@ -45,3 +45,4 @@
 #include "mcx_diag_xf.hpp"
 #include "mcx_cov.hpp"
 #include "mcx_hist.hpp"
+#include "mcx_diag_step.hpp"

@@ -155,6 +155,45 @@ def samples_hist_density(counts, edges):
     return d
 
 
+STEP_MAXBINS = 510                                              # Engine.samples_stats_step's bin count (MCMCX_STEP_MAXBINS)
+
+
+def samples_rank_scores(counts):
+    """[nfields][nbins + 2] normal scores from 1-D counts[nfields][nbins + 2] (samples_hist: one engine's, or the sum of several
+    engines'): a cell with count_b > 0 gets Phi^-1(((2 before_b + count_b + 1) / 2 - 3/8) / (n + 1/4)), the score of the average rank
+    of its values in Blom's form (Phi^-1: Wichura's AS241, PPND16), an empty cell +0.0 -- mcmcx_samples_rank_scores, pure host
+    arithmetic, no engine and no device.  With the counts' edges it is the table of `Engine.samples_stats_step` for the rank-normalised
+    split-R-hat and bulk ESS."""
+    L = _lib.load()
+    c = _i64(counts)
+    if c.ndim != 2 or c.shape[1] < 3:
+        raise McmcError("samples_rank_scores: counts must be [nfields][nbins + 2], got %s" % (c.shape,))
+    out = np.zeros(c.shape)
+    if L.mcmcx_samples_rank_scores(_lp(c), int(c.shape[0]), int(c.shape[1] - 2), _dp(out)) < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return out
+
+
+def samples_fold_scores(counts, edges, centre):
+    """The step table of the rank-normalised FOLDED values |x - centre[f]| over the cells of x: cell b of field f stands at
+    c_0 = e_0, c_b = (e_{b-1} + e_b) / 2 (1 <= b <= nbins), c_{nbins+1} = e_nbins; d_b = |c_b - centre[f]|; cells of equal d_b form one
+    group, the groups in ascending order of d_b (np.unique) are ranked with their summed counts as samples_rank_scores ranks cells, and a
+    cell gets its group's score.  counts[nfields][nbins + 2], edges[nfields][nbins + 1], centre[nfields] -> [nfields][nbins + 2]."""
+    c, e, m = _i64(counts), _f64(edges), _f64(centre).ravel()
+    if c.ndim != 2 or e.ndim != 2 or c.shape[0] != e.shape[0] or c.shape[1] != e.shape[1] + 1 or e.shape[1] < 2 or m.size != c.shape[0]:
+        raise McmcError("samples_fold_scores: counts must be [nfields][nbins + 2], edges [nfields][nbins + 1] and centre [nfields], "
+                        "got %s, %s and %s" % (c.shape, e.shape, m.shape))
+    out = np.zeros(c.shape)
+    with np.errstate(all="ignore"):
+        for f in range(c.shape[0]):
+            pos = np.concatenate([e[f, :1], (e[f, :-1] + e[f, 1:]) * 0.5, e[f, -1:]])
+            uniq, inv = np.unique(np.fabs(pos - m[f]), return_inverse=True)
+            group = np.zeros(max(uniq.size, 3), dtype=np.int64)          # a bin count of 1 at least; an empty group changes nothing
+            np.add.at(group, inv, c[f])
+            out[f] = samples_rank_scores(group[None, :])[0][inv]
+    return out
+
+
 def sample_field_names(npar, nycol=1):
     """Names of a sample's fields, in the store's order."""
     ny = int(nycol)
@@ -530,6 +569,46 @@ class Engine:
         return self._dev(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))),
                          lambda p: self.L.mcmcx_samples_stats_of_dev(self.h, int(s0), ns, int(maxlag), int(kind), _dp(av), _dp(sh), p))
 
+    # --- the summary of a step function of the retained samples (mcmcx_samples_stats_step)
+    def _stats_step_args(self, edges, table, s0, ns, shift, who):
+        """(ns, edges[nfields][nbins + 1], table[nfields][nbins + 2], shift) of a step summary"""
+        ns, _, _, nf = self._window(s0, ns)
+        ed, tb = _f64(edges), _f64(table)
+        if ed.ndim != 2 or ed.shape[0] != nf or ed.shape[1] < 2 or tb.shape != (nf, ed.shape[1] + 1):
+            raise McmcError("%s: edges must be [nfields = %d][nbins + 1] and table [nfields][nbins + 2], got %s and %s"
+                            % (who, nf, ed.shape, tb.shape))
+        return ns, ed, tb, self._shift(shift, nf, who)
+
+    def samples_stats_step(self, edges, table, s0=0, ns=None, maxlag=16, shift=None):
+        """The stats vector `samples_stats` would return if every stored value x of field f were table[f][cell_f(x)], cell_f(x) the
+        cell of `samples_hist` among edges[f] (the number of edges whose key is not above x's, 0 .. nbins + 1; at most STEP_MAXBINS
+        bins).  shift = None: u_f of chain 0 in window sample 0.  `samples_diag` finishes it; additive over engines that were given the
+        same edges, table and shift.  With edges at order statistics and `samples_rank_scores` of their counts as the table it is the
+        rank-normalised summary; with a table of zeros and ones the summary of an interval's indicator."""
+        ns, ed, tb, sh = self._stats_step_args(edges, table, s0, ns, shift, "samples_stats_step")
+        out = np.zeros(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))))
+        self._chk(self.L.mcmcx_samples_stats_step(self.h, int(s0), ns, int(maxlag), int(ed.shape[1] - 1), _dp(ed), _dp(tb), _dp(sh),
+                                                  _dp(out)))
+        return out
+
+    def samples_stats_step_torch(self, edges, table, s0=0, ns=None, maxlag=16, shift=None):
+        """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        ns, ed, tb, sh = self._stats_step_args(edges, table, s0, ns, shift, "samples_stats_step_torch")
+        return self._dev(self._chk(self.L.mcmcx_samples_stats_len(self.h, int(maxlag))),
+                         lambda p: self.L.mcmcx_samples_stats_step_dev(self.h, int(s0), ns, int(maxlag), int(ed.shape[1] - 1), _dp(ed),
+                                                                       _dp(tb), _dp(sh), p))
+
+    def samples_rank_edges(self, rank_cells=128, s0=0, ns=None):
+        """edges[nfields][rank_cells - 1] that cut the window's n = ns x nchains values of every field into rank_cells cells of (nearly)
+        equal counts: the order statistics at the 0-based ranks (k n) // rank_cells, k = 1 .. rank_cells - 1, in
+        ceil((rank_cells - 1) / QUANT_MAXR) calls of samples_order_stats."""
+        ns, _, _, nf = self._window(s0, ns)
+        B = int(rank_cells)
+        if B < 3 or B > STEP_MAXBINS + 2:
+            raise McmcError("samples_rank_edges: rank_cells must lie in 3 .. %d, got %d" % (STEP_MAXBINS + 2, B))
+        ranks = [(k * ns * self.nchains) // B for k in range(1, B)]
+        return np.concatenate([self.samples_order_stats(ranks[i:i + QUANT_MAXR], s0, ns) for i in range(0, B - 1, QUANT_MAXR)], axis=1)
+
     # --- exact order statistics, tail counts and quantiles of the retained samples (mcmcx_samples_order_stats)
     def samples_order_stats(self, ranks, s0=0, ns=None):
         """[nfields][nr]: the values whose keys are the ranks[k]-th smallest (0-based) among the ns x nchains values of each field in
@@ -566,7 +645,7 @@ class Engine:
         self._chk(self.L.mcmcx_samples_quantiles(self.h, int(s0), ns, int(p.size), _dp(p), _dp(a)))
         return a
 
-    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None, tail=False):
+    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None, tail=False, rank=False, rank_cells=128):
         """dict of arrays over the fields: mean, sd, rhat, ess, mcse, W, Bn, truncated; `fields` names the rows, `iterations` are the
         window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound.  With `probs` also the
         keys `probs` and `quantiles` ([nfields][nq], samples_quantiles of the same window).
@@ -581,7 +660,20 @@ class Engine:
           ess_quantiles   with `probs`, [nfields][nq]: the ess of the indicator x <= quantiles[f][q]; the MCSE of P(x <= q) is
                           sqrt(p (1 - p) / ess)
         An indicator that is constant over the window (a quantile at the window's extreme) gives NaN.  Cost on top of tail=False:
-        4 + nq summary passes over the window and one quantile call.  `shift` applies to the plain table only."""
+        4 + nq summary passes over the window and one quantile call.  `shift` applies to the plain table only.
+
+        rank=True adds the rank-normalised diagnostics of Vehtari et al. (2021) -- Stan's and ArviZ's `Rhat` and `ess_bulk`, which
+        mean something for a heavy-tailed field too, where rhat and ess above do not --, rank-normalised over rank_cells cells: every
+        value is replaced by the normal score of the average rank of its cell (ties as the average-rank convention treats them; at 128
+        cells within 5e-4 of the exact rank-normalised R-hat and 2.5 % of its ESS).  The recipe: edges = samples_rank_edges, counts =
+        samples_hist, table = samples_rank_scores, then samples_stats_step with a shift of zeros at the same maxlag.
+          rhat_rank       the rank-normalised split-R-hat
+          ess_bulk_rank, truncated_rank   the rank-normalised bulk ESS and its `truncated` flag
+          rhat_max        the larger of rhat_rank and the rank-normalised folded R-hat, the same summary with the table
+                          samples_fold_scores at the window's median (samples_quantiles): the scores of |x - median| over the cells of x
+        A field that is constant over the window falls into one cell and gives NaN.  Cost on top of rank=False:
+        ceil((rank_cells - 1) / 32) order-statistics calls (a radix select each: eight passes over the window), one histogram pass,
+        one quantile call and two summary passes (each reads the window twice, as every summary does)."""
         ns, oldest, thin, nf = self._window(s0, ns)
         table = samples_diag(self.samples_stats(s0, ns, maxlag, shift), nf, maxlag)
         out = {k: table[:, j].copy() for j, k in enumerate(DIAG_COLUMNS)}
@@ -606,6 +698,16 @@ class Engine:
             if probs is not None:
                 qs = out["quantiles"]
                 out["ess_quantiles"] = np.stack([of(XF_LE, qs[:, k], zero)[:, ESS] for k in range(qs.shape[1])], axis=1)
+        if rank:
+            ESS, RHAT, TRUNC = (DIAG_COLUMNS.index(k) for k in ("ess", "rhat", "truncated"))
+            zero = np.zeros(nf)
+            edges = self.samples_rank_edges(rank_cells, s0, ns)
+            counts = self.samples_hist(edges, s0, ns)
+            r = samples_diag(self.samples_stats_step(edges, samples_rank_scores(counts), s0, ns, maxlag, zero), nf, maxlag)
+            out["rhat_rank"], out["ess_bulk_rank"], out["truncated_rank"] = r[:, RHAT].copy(), r[:, ESS].copy(), r[:, TRUNC].copy()
+            fold = samples_fold_scores(counts, edges, self.samples_quantiles([0.5], s0, ns)[:, 0])
+            rf = samples_diag(self.samples_stats_step(edges, fold, s0, ns, maxlag, zero), nf, maxlag)
+            out["rhat_max"] = np.maximum(out["rhat_rank"], rf[:, RHAT])
         return out
 
     # --- marginal and pairwise joint histograms of the retained samples (mcmcx_samples_hist / _hist2)
