@@ -433,6 +433,77 @@ int mcmcx_samples_cov_dev(mcmcx_handle h, int32_t s0, int32_t ns, const double *
  * be NULL (no counterpart in the reference) */
 int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, double *cov, double *corr);
 
+/* ---- batch-means covariance of the retained samples, reduced on the device where the ring lies, on the f64 matrix cores (no
+ * counterpart in the reference): the covariance, over ALL chains, of the MEANS of batches of `batch` consecutive window samples --
+ * the one primitive behind the two joint diagnostics the per-field summary cannot give: the multivariate effective sample size
+ * (mcmcx_samples_mess, batch ~ sqrt(ns)) and the multivariate split-R-hat (mcmcx_samples_mpsrf, batch = half the window).  The
+ * covariance's kernel body with the batch accumulation in front of its staging: the same rows are streamed once, 1 / batch of the
+ * matrix instructions are issued.  Scratch, vector layout, tree and shift rule are mcmcx_samples_cov's.  No sampling kernel and no
+ * state of the run is touched.  The definition is the contract, restated bit for bit in numpy by tests/bm_ref.py:
+ *   Window: retained samples s0 .. s0 + ns - 1 of ALL chains, oldest first, under mcmcx_samples_cov's rules.  1 <= batch <= ns,
+ *   nb = ns / batch in integer division; batch k is window samples k batch .. (k + 1) batch - 1; the last ns - nb batch samples of
+ *   the window are not read.
+ *   shift_f: the caller's shift[f], or with shift == NULL field f of chain 0 in window sample 0 (mcmcx_samples_cov's rule).
+ *   Batch mean, per chain, field and batch, in IEEE doubles without contraction:
+ *     z_i = x_i - shift_f;   s = (..((z_0 + z_1) + z_2)..), the sum starting at z_0, not at +0.0;   y = s / (double)batch
+ *   Per tile of 64 chains, the covariance's order with the batch means in the place of z:
+ *     s_j  = +0.0;  for each batch k ascending, for each lane c ascending that belongs:  s_j  = s_j + y_j[k][c]
+ *     g_jk = +0.0;  for each batch k ascending, for each lane c ascending that belongs:  g_jk = fma(y_j[k][c], y_k[k][c], g_jk)
+ *   A padding lane of the last tile is selected to +0.0, not multiplied.
+ *   Across tiles: the pooled moments' fixed pairwise tree.
+ *   The vector, mcmcx_samples_cov_len doubles in the cov vector's layout:  [n_b, shift[nfields], S[nfields], G packed]
+ *   with n_b = nb * nchains, held as int64_t and returned as a double.
+ * Consequences: mcmcx_samples_cov_finish applied to it gives the mean and the covariance of the batch means.  It is additive over
+ * disjoint chain sets that used the same shift and the same batch.  With batch = 1 it has the bits of mcmcx_samples_cov's vector
+ * (y = z / 1.0 = z).
+ * mcmcx_samples_cov_bm copies the vector to host memory and synchronises; mcmcx_samples_cov_bm_dev writes it into the caller's DEVICE
+ * buffer, asynchronous on the engine's stream.  Refused with -55 (the reason in mcmcx_last_error) on the host, before anything is
+ * launched or allocated: everything mcmcx_samples_cov refuses, and a batch outside 1 .. ns. */
+/* the batch-means vector of the window to host memory (no counterpart in the reference) */
+int mcmcx_samples_cov_bm(mcmcx_handle h, int32_t s0, int32_t ns, int32_t batch, const double *shift /* [nfields] host, or NULL */,
+                         double *host_out);
+/* ... into a device buffer, asynchronous on the engine's stream (no counterpart in the reference) */
+int mcmcx_samples_cov_bm_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t batch, const double *shift, void *dev_out);
+/* The two finishes: pure host, no handle, no device, without contraction.  Both take a selection sel[nsel] of field indices (a field
+ * that is constant over the window, sspri under a flat prior, makes every matrix singular: leave it out), the cov vector
+ * (mcmcx_samples_cov) and the batch-means vector of the SAME samples; the two shifts may differ.  With [n, shift, S, G] one vector,
+ * C(vec)_jk = (G_jk - S_j * S_k / n) / (n - 1) is mcmcx_samples_cov_finish's.  Refused with -55: a null cov_vec, bm_vec, sel or out4,
+ * nfields < 1, nsel outside 1 .. nfields, a sel[j] outside 0 .. nfields - 1, an n in either vector that is below 2 or no integer,
+ * and what each states below.
+ * The Cholesky factor both use, A = R' R with R upper triangular, column by column, sums ascending, no fma:
+ *     for j = 0 .. nsel - 1:
+ *         for i = 0 .. j - 1:   t = 0;  for k = 0 .. i - 1: t = t + R_ki * R_kj;   R_ij = (A_ij - t) / R_ii
+ *         t = 0;  for k = 0 .. j - 1: t = t + R_kj * R_kj;   p = A_jj - t;   R_jj = sqrt(p)
+ * A pivot p that is not > 0 (NaN included) is no refusal: the return value is +1, a warning, and the results that need the factor
+ * are NaN.  logdet A = 2 * (..((log R_00 + log R_11) + ..), summed ascending.
+ *
+ * mcmcx_samples_mess: the multivariate effective sample size of Vats, Flegal and Jones (2019) in its replicated-batch-means form.
+ * Also refuses batch < 1 and bm_vec[0] * batch != cov_vec[0]: both vectors must cover the same nb * batch samples of every chain
+ * (hand mcmcx_samples_cov the window trimmed to nb * batch samples).  n = cov_vec[0];
+ *     Lambda = C(cov_vec)[sel, sel];   Sigma = batch * C(bm_vec)[sel, sel]
+ *     mess = n * exp((logdet Lambda - logdet Sigma) / nsel);     out4 = {mess, n, logdet Lambda, logdet Sigma}
+ *     ess_out[j] = n * Lambda_jj / Sigma_jj      (ess_out may be NULL)
+ * Sigma / n is the Monte-Carlo covariance of the mean vector: its error ellipsoid.  ess_out is the univariate batch-means ESS, a
+ * second opinion beside mcmcx_samples_diag's; mess may exceed n (antithetic chains).  A failed factor leaves its logdet and mess NaN.
+ *
+ * mcmcx_samples_mpsrf: the multivariate potential scale reduction factor of Brooks and Gelman (1998) over split chains.  cov_vec
+ * covers a window of exactly 2 n_h samples, bm_vec the same window with batch = n_h, so bm_vec[0] = M = 2 nchains split chains;
+ * also refuses n_h < 2, an odd bm_vec[0] and bm_vec[0] * n_h != cov_vec[0].  n = cov_vec[0]; per selected pair
+ *     T   = G - S * S' / n        from cov_vec           SSm = G_b - S_b * S_b' / M      from bm_vec
+ *     W   = (T - n_h * SSm) / (M * (n_h - 1))            Bn  = SSm / (M - 1)
+ *     lambda1 = the largest eigenvalue of C = R^-T Bn R^-1 with W = R' R.  The factor above decides whether W is positive definite;
+ *               for lambda1 the factor and the two triangular solves are repeated in long double (the reduction costs cond(W)
+ *               roundings of its working precision), a cyclic Jacobi on the rounded C gives the eigenvector u, and
+ *               lambda1 = u' C u / u' u
+ *     mpsrf = sqrt((n_h - 1) / n_h + lambda1);           out4 = {mpsrf, lambda1, M, n_h}
+ * W_out and Bn_out (column-major nsel x nsel, either may be NULL) take W and Bn.  With nsel = 1 this is mcmcx_samples_diag's
+ * split-R-hat; coda's factor (M + 1) / M on lambda1 is left out on purpose, so that the two agree.  mpsrf >= the split-R-hat of every
+ * selected field (the Rayleigh quotient at a unit vector).  A W that is not positive definite returns +1 with NaN in out4[0 .. 1]. */
+int mcmcx_samples_mess(const double *cov_vec, const double *bm_vec, int32_t nfields, int32_t batch, int32_t nsel, const int32_t *sel,
+                       double *out4, double *ess_out /* [nsel] or NULL */);
+int mcmcx_samples_mpsrf(const double *cov_vec, const double *bm_vec, int32_t nfields, int32_t n_h, int32_t nsel, const int32_t *sel,
+                        double *out4, double *W_out, double *Bn_out /* col-major nsel^2, or NULL */);
+
 /* ---- marginal and pairwise joint histograms of the retained samples, counted on the device where the ring lies (no counterpart in
  * the reference, whose toolchain draws its hist / dens / pairs panels from a chain file): the density of every field and of pairs of
  * fields without moving the window.  A histogram is a vector of integers and depends on no order of summation, so the results are
@@ -598,6 +669,12 @@ int mcmcx_debug_order_stats(int32_t device, int64_t n, const double *values, int
  * counts into the ring; this can.  shift: [nfields] host or NULL.  Refusals are -51. */
 int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, const double *shift,
                             double *out);
+/* The batch-means covariance's own kernels on a caller's array (no counterpart in the reference; tests only):
+ * values[ns][nfields][nchains] host laid out as mcmcx_debug_samples_cov lays it out, the padding lanes of the last tile filled with
+ * NaN by this entry; out takes the batch-means vector.  shift: [nfields] host or NULL.  Refusals are -55, what the arguments decide
+ * before a device is looked for: a null values or out, nchains or ns < 1, nfields outside 1 .. 2047, batch outside 1 .. ns. */
+int mcmcx_debug_samples_cov_bm(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, int32_t batch, const double *values,
+                               const double *shift, double *out);
 /* The histograms' own kernels on a caller's array (no counterpart in the reference; tests only): values[ns][nfields][nchains] host is
  * laid out as a store of ns slots and ceil(nchains / 64) tiles, the padding lanes of the last tile filled with NaN by this entry (a
  * kernel that counted them would show them in the last cell); out1[nfields][nbins + 2] takes the 1-D table, out2[npairs][nbins + 2]

@@ -133,6 +133,12 @@ SYMBOLS["mcmcx_samples_cov"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP,
 SYMBOLS["mcmcx_samples_cov_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _DP, C.c_void_p])
 SYMBOLS["mcmcx_samples_cov_finish"] = (C.c_int, [_DP, C.c_int32, _DP, _DP, _DP])
 SYMBOLS["mcmcx_debug_samples_cov"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP])
+# the store's batch-means covariance on the matrix cores; mcmcx_samples_mess and mcmcx_samples_mpsrf, its finishes, are pure host
+SYMBOLS["mcmcx_samples_cov_bm"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _DP])
+SYMBOLS["mcmcx_samples_cov_bm_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_void_p])
+SYMBOLS["mcmcx_samples_mess"] = (C.c_int, [_DP, _DP, C.c_int32, C.c_int32, C.c_int32, _IP, _DP, _DP])
+SYMBOLS["mcmcx_samples_mpsrf"] = (C.c_int, [_DP, _DP, C.c_int32, C.c_int32, C.c_int32, _IP, _DP, _DP, _DP])
+SYMBOLS["mcmcx_debug_samples_cov_bm"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP])
 # marginal and pairwise joint histograms of the store; mcmcx_samples_hist_edges and mcmcx_samples_hist_density are pure host
 SYMBOLS["mcmcx_samples_hist"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, _LP])
 SYMBOLS["mcmcx_samples_hist_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_void_p])

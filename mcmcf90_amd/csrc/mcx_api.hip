@@ -32,6 +32,7 @@
 #include "mcx_host_hist.hpp"
 #include "mcx_host_diag_step.hpp"
 #include "mcx_host_cov.hpp"
+#include "mcx_host_bm.hpp"
 #include "mcx_host_adapt.hpp"
 #include "mcx_host_pooled.hpp"
 #include "mcx_host_callbacks.hpp"
@@ -1157,6 +1158,44 @@ int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, d
 }
 
 
+// ------------------------------------------------------------------ the sample store's batch-means covariance and its finishes (mcx_host_bm.hpp)
+int mcmcx_samples_cov_bm_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t batch, const double *shift, void *dev_out)
+{
+    int rc = bm_check(h, s0, ns, batch, dev_out, "mcmcx_samples_cov_bm_dev"); if (rc) return rc;
+    return bm_engine(h, s0, ns, batch, shift, (double *)dev_out, nullptr);
+}
+
+int mcmcx_samples_cov_bm(mcmcx_handle h, int32_t s0, int32_t ns, int32_t batch, const double *shift, double *host_out)
+{
+    int rc = bm_check(h, s0, ns, batch, host_out, "mcmcx_samples_cov_bm"); if (rc) return rc;
+    double *staged = nullptr;
+    if ((rc = bm_engine(h, s0, ns, batch, shift, nullptr, &staged))) return rc;
+    return samples_fetch(h, host_out, staged, cov_vec_len(samples_nfields(h)) * sizeof(double));
+}
+
+int mcmcx_samples_mess(const double *cov_vec, const double *bm_vec, int32_t nfields, int32_t batch, int32_t nsel, const int32_t *sel,
+                       double *out4, double *ess_out)
+{
+    const char *who = "mcmcx_samples_mess";
+    int rc = bm_finish_check(cov_vec, bm_vec, nfields, nsel, sel, out4, who); if (rc) return rc;
+    if (batch < 1) return fail(-55, std::string(who) + ": batch < 1");
+    if (bm_vec[0] * (double)batch != cov_vec[0]) return fail(-55, std::string(who) + ": the two vectors do not cover the same samples "
+        "(bm_vec[0] * batch must be cov_vec[0])");
+    return bm_mess(cov_vec, bm_vec, nfields, batch, nsel, sel, out4, ess_out);
+}
+
+int mcmcx_samples_mpsrf(const double *cov_vec, const double *bm_vec, int32_t nfields, int32_t n_h, int32_t nsel, const int32_t *sel,
+                        double *out4, double *W_out, double *Bn_out)
+{
+    const char *who = "mcmcx_samples_mpsrf";
+    int rc = bm_finish_check(cov_vec, bm_vec, nfields, nsel, sel, out4, who); if (rc) return rc;
+    if (n_h < 2) return fail(-55, std::string(who) + ": n_h < 2");
+    const double M = bm_vec[0];
+    if (M != 2.0 * std::floor(M / 2.0) || M * (double)n_h != cov_vec[0]) return fail(-55, std::string(who) + ": bm_vec must hold the two "
+        "half-window means of every chain (bm_vec[0] even, bm_vec[0] * n_h = cov_vec[0])");
+    return bm_mpsrf(cov_vec, bm_vec, nfields, n_h, nsel, sel, out4, W_out, Bn_out);
+}
+
 // ------------------------------------------------------------------ marginal and joint histograms of the store (mcx_host_hist.hpp)
 int mcmcx_samples_hist_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges, void *dev_out)
 {
@@ -1419,6 +1458,38 @@ int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, in
     const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
     double *dout = w + (size_t)T * cov_row_len(nfields) + (size_t)nfields;
     int rc = cov_launch(W, w, shift, dout, 0); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(0));
+    HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the batch-means covariance's own kernels on a caller's array, as mcmcx_debug_samples_cov lays it out: values[ns][nfields][nchains], the
+// padding lanes of the last tile hold NaN, which a kernel that summed or multiplied them would spread
+int mcmcx_debug_samples_cov_bm(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, int32_t batch, const double *values,
+                               const double *shift, double *out)
+{
+    if (!values || !out) return fail(-55, "mcmcx_debug_samples_cov_bm: null argument");
+    if (nchains < 1 || nfields < 1 || nfields > 2047 || ns < 1) return fail(-55, "mcmcx_debug_samples_cov_bm: nchains, ns < 1 or nfields "
+        "outside 1 .. 2047");
+    if (batch < 1 || batch > ns) return fail(-55, "mcmcx_debug_samples_cov_bm: batch outside 1 .. ns");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const int T = (nchains + 63) / 64;
+    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
+    std::vector<double> host(words, std::nan(""));
+    for (int s = 0; s < ns; ++s)
+        for (int f = 0; f < nfields; ++f)
+            for (int c = 0; c < nchains; ++c)
+                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
+                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
+    DevBufs g;
+    double *store = nullptr, *w = nullptr;
+    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, cov_scratch_len(T, nfields) * 8));
+    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
+    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
+    double *dout = w + (size_t)T * cov_row_len(nfields) + (size_t)nfields;
+    int rc = bm_launch(W, batch, w, shift, dout, 0); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(0));
     HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
     return 0;

@@ -24,6 +24,7 @@
 //   mcx_diag.hpp      diag_tile_kernel<W>, diag_shift_kernel, diag_pack_kernel (the store's convergence summary, reduced where it lies)
 //   mcx_quant.hpp     quant_hist_kernel / quant_pick_kernel / quant_counts_kernel<NQ> (the store's order statistics and tail counts)
 //   mcx_cov.hpp       cov_tile_kernel<NS, OFF>, cov_pack_kernel (the store's posterior covariance on the f64 matrix cores)
+//   mcx_bm.hpp        bm_tile_kernel<NS, OFF> (the store's batch-means covariance: multivariate ESS and R-hat are finished from it)
 //   mcx_hist.hpp      hist_kernel / hist2_kernel (the store's marginal and pairwise joint histograms, counted in LDS)
 // The lane-GROUP kernels (16 / 4 lanes per chain, factors on chip) are mcx_group.hpp and mcx_group_ram.hpp.
 // Kernel forms that were measured and lost, or that a later form superseded, are not in the product library: tools/variants/README.md.
@@ -44,5 +45,6 @@
 #include "mcx_quant.hpp"
 #include "mcx_diag_xf.hpp"
 #include "mcx_cov.hpp"
+#include "mcx_bm.hpp"
 #include "mcx_hist.hpp"
 #include "mcx_diag_step.hpp"

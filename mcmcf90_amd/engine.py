@@ -105,6 +105,55 @@ def samples_cov_finish(vec, nfields):
     return mean, cov, corr                                      # symmetric: column-major is row-major
 
 
+def _sel(sel, nfields, who):
+    """a field selection as a contiguous int32 array"""
+    idx = np.ascontiguousarray(np.asarray(sel, dtype=np.int32).ravel())
+    if idx.size < 1 or idx.size > int(nfields):
+        raise McmcError("%s: %d fields selected of %d" % (who, idx.size, int(nfields)))
+    return idx
+
+
+def _two_vectors(cov_vec, bm_vec, nfields, who):
+    cv, bv = _f64(cov_vec), _f64(bm_vec)
+    for v in (cv, bv):
+        if v.size != samples_cov_len(nfields):
+            raise McmcError("%s: %d doubles given, nfields %d makes %d" % (who, v.size, int(nfields), samples_cov_len(nfields)))
+    return cv, bv
+
+
+def samples_mess(cov_vec, bm_vec, nfields, batch, sel):
+    """dict: `mess`, the multivariate effective sample size of the fields `sel` (Vats, Flegal, Jones 2019, replicated batch means), `n`,
+    `logdet_lambda`, `logdet_sigma`, `ess_bm` [nsel] (the univariate batch-means ESS of each selected field) and `warn` (1: a matrix was
+    not positive definite -- a constant field was selected -- and the results are NaN) from a cov vector and the batch-means vector of the
+    same nb x batch samples (one engine's each, or sums over engines): mcmcx_samples_mess, pure host, no engine and no device."""
+    L = _lib.load()
+    nf = int(nfields)
+    cv, bv = _two_vectors(cov_vec, bm_vec, nf, "samples_mess")
+    idx = _sel(sel, nf, "samples_mess")
+    out4, ess = np.zeros(4), np.zeros(idx.size)
+    rc = L.mcmcx_samples_mess(_dp(cv), _dp(bv), nf, int(batch), int(idx.size), idx.ctypes.data_as(C.POINTER(C.c_int32)), _dp(out4), _dp(ess))
+    if rc < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return {"mess": out4[0], "n": out4[1], "logdet_lambda": out4[2], "logdet_sigma": out4[3], "ess_bm": ess, "warn": int(rc)}
+
+
+def samples_mpsrf(cov_vec, bm_vec, nfields, n_h, sel):
+    """dict: `mpsrf`, the multivariate split-R-hat of the fields `sel` (Brooks and Gelman 1998, without coda's (M + 1) / M: with one field it
+    is samples_diag's rhat), `lambda1`, `M` (split chains), `n_h`, `W` and `Bn` [nsel][nsel], and `warn` (1: W was not positive definite,
+    mpsrf is NaN) from the cov vector of a window of 2 n_h samples and the batch-means vector of the same window with batch = n_h:
+    mcmcx_samples_mpsrf, pure host, no engine and no device."""
+    L = _lib.load()
+    nf = int(nfields)
+    cv, bv = _two_vectors(cov_vec, bm_vec, nf, "samples_mpsrf")
+    idx = _sel(sel, nf, "samples_mpsrf")
+    out4, W, Bn = np.zeros(4), np.zeros((idx.size, idx.size)), np.zeros((idx.size, idx.size))
+    rc = L.mcmcx_samples_mpsrf(_dp(cv), _dp(bv), nf, int(n_h), int(idx.size), idx.ctypes.data_as(C.POINTER(C.c_int32)), _dp(out4), _dp(W),
+                               _dp(Bn))
+    if rc < 0:
+        raise McmcError(L.mcmcx_last_error().decode())
+    return {"mpsrf": out4[0], "lambda1": out4[1], "M": out4[2], "n_h": out4[3], "W": W, "Bn": Bn, "warn": int(rc)}      # symmetric
+
+
 QUANT_MAXR = 32
 
 
@@ -645,7 +694,7 @@ class Engine:
         self._chk(self.L.mcmcx_samples_quantiles(self.h, int(s0), ns, int(p.size), _dp(p), _dp(a)))
         return a
 
-    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None, tail=False, rank=False, rank_cells=128):
+    def samples_summary(self, s0=0, ns=None, maxlag=16, shift=None, probs=None, tail=False, rank=False, rank_cells=128, multivariate=False):
         """dict of arrays over the fields: mean, sd, rhat, ess, mcse, W, Bn, truncated; `fields` names the rows, `iterations` are the
         window's.  truncated = 1: the lag window ended before the autocorrelation did, ess is an upper bound.  With `probs` also the
         keys `probs` and `quantiles` ([nfields][nq], samples_quantiles of the same window).
@@ -673,7 +722,14 @@ class Engine:
                           samples_fold_scores at the window's median (samples_quantiles): the scores of |x - median| over the cells of x
         A field that is constant over the window falls into one cell and gives NaN.  Cost on top of rank=False:
         ceil((rank_cells - 1) / 32) order-statistics calls (a radix select each: eight passes over the window), one histogram pass,
-        one quantile call and two summary passes (each reads the window twice, as every summary does)."""
+        one quantile call and two summary passes (each reads the window twice, as every summary does).
+
+        multivariate=True adds the joint diagnostics of the parameter block, at the table's mean as the shift (samples_mess and
+        samples_mpsrf have the definitions):
+          mess            the multivariate effective sample size of theta at batch = floor(sqrt(ns)); `mess_batch` is that batch
+          ess_bm          [npar]: the univariate batch-means ESS of every parameter at the same batch
+          mpsrf           the multivariate split-R-hat of theta: at least every parameter's rhat
+        Cost on top of multivariate=False: four passes over the window (two covariances, two batch-means covariances)."""
         ns, oldest, thin, nf = self._window(s0, ns)
         table = samples_diag(self.samples_stats(s0, ns, maxlag, shift), nf, maxlag)
         out = {k: table[:, j].copy() for j, k in enumerate(DIAG_COLUMNS)}
@@ -708,6 +764,10 @@ class Engine:
             fold = samples_fold_scores(counts, edges, self.samples_quantiles([0.5], s0, ns)[:, 0])
             rf = samples_diag(self.samples_stats_step(edges, fold, s0, ns, maxlag, zero), nf, maxlag)
             out["rhat_max"] = np.maximum(out["rhat_rank"], rf[:, RHAT])
+        if multivariate:
+            m = self.samples_mess(s0, ns, None, "theta", out["mean"])
+            out["mess"], out["mess_batch"], out["ess_bm"] = m["mess"], m["batch"], m["ess_bm"]
+            out["mpsrf"] = self.samples_mpsrf(s0, ns, "theta", out["mean"])["mpsrf"]
         return out
 
     # --- marginal and pairwise joint histograms of the retained samples (mcmcx_samples_hist / _hist2)
@@ -791,6 +851,62 @@ class Engine:
         k = self.npar if fields == "theta" else nf
         names = sample_field_names(self.npar, getattr(self, "nycol", 1))
         return {"fields": names[:k], "mean": mean[:k].copy(), "cov": cov[:k, :k].copy(), "corr": corr[:k, :k].copy(), "n": int(vec[0])}
+
+    # --- batch-means covariance of the retained samples and its finishes (mcmcx_samples_cov_bm, mcmcx_samples_mess / _mpsrf)
+    def samples_cov_bm_stats(self, batch, s0=0, ns=None, shift=None):
+        """The batch-means vector of retained samples s0 .. s0 + ns - 1 of all chains (include/mcmcx.h has the definition): the cov
+        vector of the means of batches of `batch` consecutive samples, additive over engines that were given the same `shift` and
+        `batch`; `samples_mess` and `samples_mpsrf` finish it beside a cov vector, `samples_cov_finish` gives the batch means' moments."""
+        ns, _, _, nf = self._window(s0, ns)
+        sh = self._shift(shift, nf, "samples_cov_bm_stats")
+        a = np.zeros(self._chk(self.L.mcmcx_samples_cov_len(self.h)))
+        self._chk(self.L.mcmcx_samples_cov_bm(self.h, int(s0), ns, int(batch), _dp(sh), _dp(a)))
+        return a
+
+    def samples_cov_bm_stats_torch(self, batch, s0=0, ns=None, shift=None):
+        """The same vector as a float64 torch tensor on the engine's device, filled by the asynchronous form and synchronised."""
+        ns, _, _, nf = self._window(s0, ns)
+        sh = self._shift(shift, nf, "samples_cov_bm_stats_torch")
+        return self._dev(self._chk(self.L.mcmcx_samples_cov_len(self.h)),
+                         lambda p: self.L.mcmcx_samples_cov_bm_dev(self.h, int(s0), ns, int(batch), _dp(sh), p))
+
+    def _joint_args(self, s0, ns, fields, shift, who):
+        """(ns, nfields, selection, shift) of a joint diagnostic"""
+        ns, _, _, nf = self._window(s0, ns)
+        if isinstance(fields, str):
+            if fields not in ("theta", "all"):
+                raise McmcError("%s: fields must be 'theta', 'all' or a list of field indices" % who)
+            fields = range(self.npar if fields == "theta" else nf)
+        if isinstance(shift, str):
+            if shift != "mean":
+                raise McmcError("%s: shift must be None, 'mean' or an array" % who)
+            shift = samples_diag(self.samples_stats(s0, ns, 0), nf, 0)[:, 0].copy()
+        return ns, nf, _sel(list(fields), nf, who), shift
+
+    def samples_mess(self, s0=0, ns=None, batch=None, fields="theta", shift="mean"):
+        """The multivariate effective sample size of the window for the mean VECTOR of `fields` ("theta", "all" or field indices; leave
+        a field out that is constant over the window): the module function samples_mess's dict with `batch` and `fields` added.  batch =
+        floor(sqrt(ns)) by default; the window is trimmed to nb x batch samples for both vectors.  shift="mean" takes the mean of
+        samples_stats(maxlag=0) first."""
+        ns, nf, idx, shift = self._joint_args(s0, ns, fields, shift, "samples_mess")
+        b = int(np.floor(np.sqrt(ns))) if batch is None else int(batch)
+        if b < 1 or b > ns:
+            raise McmcError("samples_mess: a batch of %d samples in a window of %d" % (b, ns))
+        used = (ns // b) * b
+        out = samples_mess(self.samples_cov_stats(s0, used, shift), self.samples_cov_bm_stats(b, s0, used, shift), nf, b, idx)
+        out["batch"], out["fields"] = b, [sample_field_names(self.npar, getattr(self, "nycol", 1))[j] for j in idx]
+        return out
+
+    def samples_mpsrf(self, s0=0, ns=None, fields="theta", shift="mean"):
+        """The multivariate split-R-hat of the window over `fields`: the module function samples_mpsrf's dict with `fields` added; an odd
+        window loses its last sample.  It is at least the split-R-hat of every selected field, and can be far above all of them."""
+        ns, nf, idx, shift = self._joint_args(s0, ns, fields, shift, "samples_mpsrf")
+        nh = ns // 2
+        if nh < 2:
+            raise McmcError("samples_mpsrf: a window of %d samples, four at least" % ns)
+        out = samples_mpsrf(self.samples_cov_stats(s0, 2 * nh, shift), self.samples_cov_bm_stats(nh, s0, 2 * nh, shift), nf, nh, idx)
+        out["fields"] = [sample_field_names(self.npar, getattr(self, "nycol", 1))[j] for j in idx]
+        return out
 
     def pooled_moments(self):
         n = self.L.mcmcx_pooled_moments_len(self.h)
