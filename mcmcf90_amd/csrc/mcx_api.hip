@@ -1008,52 +1008,38 @@ int32_t mcmcx_samples_stats_len(mcmcx_handle h, int32_t maxlag)
 
 int mcmcx_samples_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, void *dev_out)
 {
-    int rc = diag_check(h, s0, ns, maxlag, dev_out, "mcmcx_samples_stats_dev"); if (rc) return rc;
-    return diag_engine(h, s0, ns, maxlag, XF_IDENTITY, nullptr, shift, (double *)dev_out, nullptr);
+    return diag_run(h, s0, ns, maxlag, XF_IDENTITY, nullptr, shift, dev_out, nullptr, "mcmcx_samples_stats_dev");
 }
 
 int mcmcx_samples_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, const double *shift, double *host_out)
 {
-    int rc = diag_check(h, s0, ns, maxlag, host_out, "mcmcx_samples_stats"); if (rc) return rc;
-    double *staged = nullptr;
-    if ((rc = diag_engine(h, s0, ns, maxlag, XF_IDENTITY, nullptr, shift, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
+    return diag_run(h, s0, ns, maxlag, XF_IDENTITY, nullptr, shift, nullptr, host_out, "mcmcx_samples_stats");
 }
 
 // ... of an elementwise function of the stored values (mcx_diag_xf.hpp): kind 0 runs the summary's own kernels
 int mcmcx_samples_stats_of_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t kind, const double *a, const double *shift,
                                void *dev_out)
 {
-    int rc = diag_xf_check(kind, a, "mcmcx_samples_stats_of_dev"); if (rc) return rc;
-    if ((rc = diag_check(h, s0, ns, maxlag, dev_out, "mcmcx_samples_stats_of_dev", -53))) return rc;
-    return diag_engine(h, s0, ns, maxlag, kind, a, shift, (double *)dev_out, nullptr);
+    return diag_run(h, s0, ns, maxlag, kind, a, shift, dev_out, nullptr, "mcmcx_samples_stats_of_dev", -53);
 }
 
 int mcmcx_samples_stats_of(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t kind, const double *a, const double *shift,
                            double *host_out)
 {
-    int rc = diag_xf_check(kind, a, "mcmcx_samples_stats_of"); if (rc) return rc;
-    if ((rc = diag_check(h, s0, ns, maxlag, host_out, "mcmcx_samples_stats_of", -53))) return rc;
-    double *staged = nullptr;
-    if ((rc = diag_engine(h, s0, ns, maxlag, kind, a, shift, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
+    return diag_run(h, s0, ns, maxlag, kind, a, shift, nullptr, host_out, "mcmcx_samples_stats_of", -53);
 }
 
 // ... of a step function of the stored values, u_f(x) = table_f[cell_f(x)] (mcx_diag_step.hpp)
 int mcmcx_samples_stats_step_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t nbins, const double *edges,
                                  const double *table, const double *shift, void *dev_out)
 {
-    int rc = diag_step_check(h, s0, ns, maxlag, nbins, edges, table, dev_out, "mcmcx_samples_stats_step_dev"); if (rc) return rc;
-    return diag_step_engine(h, s0, ns, maxlag, nbins, edges, table, shift, (double *)dev_out, nullptr);
+    return diag_step_run(h, s0, ns, maxlag, nbins, edges, table, shift, dev_out, nullptr, "mcmcx_samples_stats_step_dev");
 }
 
 int mcmcx_samples_stats_step(mcmcx_handle h, int32_t s0, int32_t ns, int32_t maxlag, int32_t nbins, const double *edges,
                              const double *table, const double *shift, double *host_out)
 {
-    int rc = diag_step_check(h, s0, ns, maxlag, nbins, edges, table, host_out, "mcmcx_samples_stats_step"); if (rc) return rc;
-    double *staged = nullptr;
-    if ((rc = diag_step_engine(h, s0, ns, maxlag, nbins, edges, table, shift, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, (size_t)diag_stats_len(samples_nfields(h), maxlag) * sizeof(double));
+    return diag_step_run(h, s0, ns, maxlag, nbins, edges, table, shift, nullptr, host_out, "mcmcx_samples_stats_step");
 }
 
 // the table of normal scores from 1-D histogram counts: pure host, no handle, no device
@@ -1078,32 +1064,22 @@ int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, dou
 // ------------------------------------------------------------------ order statistics, counts, quantiles of the store (mcx_host_quant.hpp)
 int mcmcx_samples_order_stats_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr, const int64_t *ranks, void *dev_out)
 {
-    int rc = quant_check(h, s0, ns, nr, ranks, dev_out, "mcmcx_samples_order_stats_dev"); if (rc) return rc;
-    if ((rc = quant_check_ranks((long long)ns * h->cfg.nchains, nr, ranks, "mcmcx_samples_order_stats_dev"))) return rc;
-    return quant_order_stats(h, s0, ns, nr, ranks, (double *)dev_out, nullptr);
+    return quant_order_stats_run(h, s0, ns, nr, ranks, dev_out, nullptr, "mcmcx_samples_order_stats_dev");
 }
 
 int mcmcx_samples_order_stats(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nr, const int64_t *ranks, double *host_out)
 {
-    int rc = quant_check(h, s0, ns, nr, ranks, host_out, "mcmcx_samples_order_stats"); if (rc) return rc;
-    if ((rc = quant_check_ranks((long long)ns * h->cfg.nchains, nr, ranks, "mcmcx_samples_order_stats"))) return rc;
-    double *staged = nullptr;
-    if ((rc = quant_order_stats(h, s0, ns, nr, ranks, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, (size_t)samples_nfields(h) * (size_t)nr * sizeof(double));
+    return quant_order_stats_run(h, s0, ns, nr, ranks, nullptr, host_out, "mcmcx_samples_order_stats");
 }
 
 int mcmcx_samples_counts_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, void *dev_out)
 {
-    int rc = quant_check(h, s0, ns, nq, x, dev_out, "mcmcx_samples_counts_dev"); if (rc) return rc;
-    return quant_counts(h, s0, ns, nq, x, (unsigned long long *)dev_out, nullptr);
+    return quant_counts_run(h, s0, ns, nq, x, dev_out, nullptr, "mcmcx_samples_counts_dev");
 }
 
 int mcmcx_samples_counts(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nq, const double *x, int64_t *host_out)
 {
-    int rc = quant_check(h, s0, ns, nq, x, host_out, "mcmcx_samples_counts"); if (rc) return rc;
-    unsigned long long *staged = nullptr;
-    if ((rc = quant_counts(h, s0, ns, nq, x, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, (size_t)samples_nfields(h) * (size_t)nq * 2 * sizeof(int64_t));
+    return quant_counts_run(h, s0, ns, nq, x, nullptr, host_out, "mcmcx_samples_counts");
 }
 
 int mcmcx_samples_quantile_ranks(int64_t n, int32_t nq, const double *probs, int64_t *ranks, double *frac)
@@ -1138,16 +1114,12 @@ int32_t mcmcx_samples_cov_len(mcmcx_handle h)
 
 int mcmcx_samples_cov_dev(mcmcx_handle h, int32_t s0, int32_t ns, const double *shift, void *dev_out)
 {
-    int rc = cov_check(h, s0, ns, dev_out, "mcmcx_samples_cov_dev"); if (rc) return rc;
-    return cov_engine(h, s0, ns, shift, (double *)dev_out, nullptr);
+    return cov_run(h, s0, ns, shift, dev_out, nullptr, "mcmcx_samples_cov_dev");
 }
 
 int mcmcx_samples_cov(mcmcx_handle h, int32_t s0, int32_t ns, const double *shift, double *host_out)
 {
-    int rc = cov_check(h, s0, ns, host_out, "mcmcx_samples_cov"); if (rc) return rc;
-    double *staged = nullptr;
-    if ((rc = cov_engine(h, s0, ns, shift, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, cov_vec_len(samples_nfields(h)) * sizeof(double));
+    return cov_run(h, s0, ns, shift, nullptr, host_out, "mcmcx_samples_cov");
 }
 
 int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, double *cov, double *corr)
@@ -1161,16 +1133,12 @@ int mcmcx_samples_cov_finish(const double *vec, int32_t nfields, double *mean, d
 // ------------------------------------------------------------------ the sample store's batch-means covariance and its finishes (mcx_host_bm.hpp)
 int mcmcx_samples_cov_bm_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t batch, const double *shift, void *dev_out)
 {
-    int rc = bm_check(h, s0, ns, batch, dev_out, "mcmcx_samples_cov_bm_dev"); if (rc) return rc;
-    return bm_engine(h, s0, ns, batch, shift, (double *)dev_out, nullptr);
+    return bm_run(h, s0, ns, batch, shift, dev_out, nullptr, "mcmcx_samples_cov_bm_dev");
 }
 
 int mcmcx_samples_cov_bm(mcmcx_handle h, int32_t s0, int32_t ns, int32_t batch, const double *shift, double *host_out)
 {
-    int rc = bm_check(h, s0, ns, batch, host_out, "mcmcx_samples_cov_bm"); if (rc) return rc;
-    double *staged = nullptr;
-    if ((rc = bm_engine(h, s0, ns, batch, shift, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, cov_vec_len(samples_nfields(h)) * sizeof(double));
+    return bm_run(h, s0, ns, batch, shift, nullptr, host_out, "mcmcx_samples_cov_bm");
 }
 
 int mcmcx_samples_mess(const double *cov_vec, const double *bm_vec, int32_t nfields, int32_t batch, int32_t nsel, const int32_t *sel,
@@ -1199,32 +1167,24 @@ int mcmcx_samples_mpsrf(const double *cov_vec, const double *bm_vec, int32_t nfi
 // ------------------------------------------------------------------ marginal and joint histograms of the store (mcx_host_hist.hpp)
 int mcmcx_samples_hist_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges, void *dev_out)
 {
-    int rc = hist_check(h, s0, ns, false, 0, nullptr, nbins, edges, dev_out, "mcmcx_samples_hist_dev"); if (rc) return rc;
-    return hist_engine(h, s0, ns, nbins, edges, 0, nullptr, (unsigned long long *)dev_out, nullptr);
+    return hist_run(h, s0, ns, false, 0, nullptr, nbins, edges, dev_out, nullptr, "mcmcx_samples_hist_dev");
 }
 
 int mcmcx_samples_hist(mcmcx_handle h, int32_t s0, int32_t ns, int32_t nbins, const double *edges, int64_t *host_out)
 {
-    int rc = hist_check(h, s0, ns, false, 0, nullptr, nbins, edges, host_out, "mcmcx_samples_hist"); if (rc) return rc;
-    unsigned long long *staged = nullptr;
-    if ((rc = hist_engine(h, s0, ns, nbins, edges, 0, nullptr, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, hist_table_words(samples_nfields(h), 0, nbins) * sizeof(int64_t));
+    return hist_run(h, s0, ns, false, 0, nullptr, nbins, edges, nullptr, host_out, "mcmcx_samples_hist");
 }
 
 int mcmcx_samples_hist2_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t npairs, const int32_t *pairs, int32_t nbins,
                             const double *edges, void *dev_out)
 {
-    int rc = hist_check(h, s0, ns, true, npairs, pairs, nbins, edges, dev_out, "mcmcx_samples_hist2_dev"); if (rc) return rc;
-    return hist_engine(h, s0, ns, nbins, edges, npairs, pairs, (unsigned long long *)dev_out, nullptr);
+    return hist_run(h, s0, ns, true, npairs, pairs, nbins, edges, dev_out, nullptr, "mcmcx_samples_hist2_dev");
 }
 
 int mcmcx_samples_hist2(mcmcx_handle h, int32_t s0, int32_t ns, int32_t npairs, const int32_t *pairs, int32_t nbins, const double *edges,
                         int64_t *host_out)
 {
-    int rc = hist_check(h, s0, ns, true, npairs, pairs, nbins, edges, host_out, "mcmcx_samples_hist2"); if (rc) return rc;
-    unsigned long long *staged = nullptr;
-    if ((rc = hist_engine(h, s0, ns, nbins, edges, npairs, pairs, nullptr, &staged))) return rc;
-    return samples_fetch(h, host_out, staged, hist_table_words(samples_nfields(h), npairs, nbins) * sizeof(int64_t));
+    return hist_run(h, s0, ns, true, npairs, pairs, nbins, edges, nullptr, host_out, "mcmcx_samples_hist2");
 }
 
 int mcmcx_samples_hist_edges(double lo, double hi, int32_t nbins, double *edges_out)
@@ -1440,27 +1400,12 @@ int mcmcx_debug_samples_cov(int32_t device, int32_t nchains, int32_t nfields, in
     if (!values || !out) return fail(-51, "mcmcx_debug_samples_cov: null argument");
     if (nchains < 1 || nfields < 1 || nfields > 2047 || ns < 1) return fail(-51, "mcmcx_debug_samples_cov: nchains, ns < 1 or nfields "
         "outside 1 .. 2047");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    const int T = (nchains + 63) / 64;
-    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
-    std::vector<double> host(words, std::nan(""));
-    for (int s = 0; s < ns; ++s)
-        for (int f = 0; f < nfields; ++f)
-            for (int c = 0; c < nchains; ++c)
-                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
-                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
-    DevBufs g;
-    double *store = nullptr, *w = nullptr;
-    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, cov_scratch_len(T, nfields) * 8));
-    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
-    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
-    double *dout = w + (size_t)T * cov_row_len(nfields) + (size_t)nfields;
-    int rc = cov_launch(W, w, shift, dout, 0); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t work = cov_work_len((nchains + 63) / 64, nfields), vlen = cov_vec_len(nfields);
+    DebugStore D;
+    int rc = D.open(device, nchains, nfields, ns, values, (work + vlen) * 8); if (rc) return rc;
+    double *w = (double *)D.scratch;
+    if ((rc = cov_launch(D.win, w, shift, w + work, 0))) return rc;
+    return D.fetch(out, w + work, vlen * 8);
 }
 
 // the batch-means covariance's own kernels on a caller's array, as mcmcx_debug_samples_cov lays it out: values[ns][nfields][nchains], the
@@ -1472,27 +1417,12 @@ int mcmcx_debug_samples_cov_bm(int32_t device, int32_t nchains, int32_t nfields,
     if (nchains < 1 || nfields < 1 || nfields > 2047 || ns < 1) return fail(-55, "mcmcx_debug_samples_cov_bm: nchains, ns < 1 or nfields "
         "outside 1 .. 2047");
     if (batch < 1 || batch > ns) return fail(-55, "mcmcx_debug_samples_cov_bm: batch outside 1 .. ns");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    const int T = (nchains + 63) / 64;
-    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
-    std::vector<double> host(words, std::nan(""));
-    for (int s = 0; s < ns; ++s)
-        for (int f = 0; f < nfields; ++f)
-            for (int c = 0; c < nchains; ++c)
-                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
-                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
-    DevBufs g;
-    double *store = nullptr, *w = nullptr;
-    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, cov_scratch_len(T, nfields) * 8));
-    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
-    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
-    double *dout = w + (size_t)T * cov_row_len(nfields) + (size_t)nfields;
-    int rc = bm_launch(W, batch, w, shift, dout, 0); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(out, dout, cov_vec_len(nfields) * 8, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t work = cov_work_len((nchains + 63) / 64, nfields), vlen = cov_vec_len(nfields);
+    DebugStore D;
+    int rc = D.open(device, nchains, nfields, ns, values, (work + vlen) * 8); if (rc) return rc;
+    double *w = (double *)D.scratch;
+    if ((rc = bm_launch(D.win, batch, w, shift, w + work, 0))) return rc;
+    return D.fetch(out, w + work, vlen * 8);
 }
 
 // the summary's own kernels, of u(x), on a caller's array: a store of ns slots, ceil(nchains / 64) tiles and nfields fields filled from
@@ -1507,28 +1437,12 @@ int mcmcx_debug_samples_stats(int32_t device, int32_t nchains, int32_t nfields, 
     if (nchains < 1 || nfields < 1 || ns < 4) return fail(-53, std::string(who) + ": nchains, nfields < 1 or ns < 4");
     if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-53, std::string(who) + ": maxlag " + std::to_string(maxlag) +
         " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    const int T = (nchains + 63) / 64;
-    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
-    std::vector<double> host(words, std::nan(""));
-    for (int s = 0; s < ns; ++s)
-        for (int f = 0; f < nfields; ++f)
-            for (int c = 0; c < nchains; ++c)
-                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
-                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
-    const size_t need = diag_scratch_len(T, nfields, maxlag, kind), slen = (size_t)diag_stats_len(nfields, maxlag);
-    DevBufs g;
-    double *store = nullptr, *w = nullptr;
-    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, need * 8));
-    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
-    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
-    double *dout = w + need - slen;
-    if ((rc = diag_launch(W, w, maxlag, kind, a, shift, dout, 0))) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(out, dout, slen * 8, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t work = diag_work_len((nchains + 63) / 64, nfields, maxlag, kind), slen = (size_t)diag_stats_len(nfields, maxlag);
+    DebugStore D;
+    if ((rc = D.open(device, nchains, nfields, ns, values, (work + slen) * 8))) return rc;
+    double *w = (double *)D.scratch;
+    if ((rc = diag_launch(D.win, w, maxlag, kind, a, shift, w + work, 0))) return rc;
+    return D.fetch(out, w + work, slen * 8);
 }
 
 // the step summary's own kernels on a caller's array, laid out as mcmcx_debug_samples_stats lays it out: the padding lanes of the last
@@ -1543,28 +1457,12 @@ int mcmcx_debug_samples_stats_step(int32_t device, int32_t nchains, int32_t nfie
     if (maxlag < 0 || maxlag > MCMCX_DIAG_MAXLAG) return fail(-54, std::string(who) + ": maxlag " + std::to_string(maxlag) +
         " outside 0 .. " + std::to_string(MCMCX_DIAG_MAXLAG));
     if ((rc = hist_check_edges(edges, nfields, nbins, who, -54))) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    const int T = (nchains + 63) / 64;
-    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
-    std::vector<double> host(words, std::nan(""));
-    for (int s = 0; s < ns; ++s)
-        for (int f = 0; f < nfields; ++f)
-            for (int c = 0; c < nchains; ++c)
-                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
-                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
-    const size_t need = diag_step_scratch_len(T, nfields, maxlag, nbins), slen = (size_t)diag_stats_len(nfields, maxlag);
-    DevBufs g;
-    double *store = nullptr, *w = nullptr;
-    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, need * 8));
-    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
-    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
-    double *dout = w + need - slen;
-    if ((rc = diag_step_launch(W, w, maxlag, nbins, edges, table, shift, dout, 0))) return rc;
-    HIPCHK(hipStreamSynchronize(0));
-    HIPCHK(hipMemcpy(out, dout, slen * 8, hipMemcpyDeviceToHost));
-    return 0;
+    const size_t work = diag_step_work_len((nchains + 63) / 64, nfields, maxlag, nbins), slen = (size_t)diag_stats_len(nfields, maxlag);
+    DebugStore D;
+    if ((rc = D.open(device, nchains, nfields, ns, values, (work + slen) * 8))) return rc;
+    double *w = (double *)D.scratch;
+    if ((rc = diag_step_launch(D.win, w, maxlag, nbins, edges, table, shift, w + work, 0))) return rc;
+    return D.fetch(out, w + work, slen * 8);
 }
 
 // the histograms' own kernels on a caller's array: a store of ns slots, ceil(nchains / 64) tiles and nfields fields filled from
@@ -1580,35 +1478,14 @@ int mcmcx_debug_samples_hist(int32_t device, int32_t nchains, int32_t nfields, i
     if (nchains < 1 || nfields < 1 || ns < 1 || chunk < 0) return fail(-52, std::string(who) + ": nchains, nfields, ns < 1 or chunk < 0");
     if ((rc = hist_check_edges(edges, nfields, nbins, who))) return rc;
     if (out2 && (rc = hist_check_pairs(pairs, npairs, nfields, who))) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    const int T = (nchains + 63) / 64;
-    const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
-    std::vector<double> host(words, std::nan(""));
-    for (int s = 0; s < ns; ++s)
-        for (int f = 0; f < nfields; ++f)
-            for (int c = 0; c < nchains; ++c)
-                host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
-                    values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
     const size_t m = hist_key_words(nfields, nbins), n1 = hist_table_words(nfields, 0, nbins);
     const size_t n2 = out2 ? hist_table_words(nfields, npairs, nbins) : 0;
-    DevBufs g;
-    double *store = nullptr; unsigned long long *w = nullptr;
-    HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&w, (m + std::max(n1, n2)) * 8));
-    HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
-    const SampleWin W = {store, 0, (size_t)ns, T, nfields, nchains, ns};
-    const QuantWin A = hist_window(W, chunk);
-    if (out1) {
-        if ((rc = hist_launch(A, w, nbins, edges, 0, nullptr, w + m, 0))) return rc;
-        HIPCHK(hipStreamSynchronize(0));
-        HIPCHK(hipMemcpy(out1, w + m, n1 * 8, hipMemcpyDeviceToHost));
-    }
-    if (out2) {
-        if ((rc = hist_launch(A, w, nbins, edges, npairs, pairs, w + m, 0))) return rc;
-        HIPCHK(hipStreamSynchronize(0));
-        HIPCHK(hipMemcpy(out2, w + m, n2 * 8, hipMemcpyDeviceToHost));
-    }
+    DebugStore D;
+    if ((rc = D.open(device, nchains, nfields, ns, values, (m + std::max(n1, n2)) * 8))) return rc;
+    unsigned long long *w = (unsigned long long *)D.scratch;
+    const QuantWin A = hist_window(D.win, chunk);
+    if (out1 && ((rc = hist_launch(A, w, nbins, edges, 0, nullptr, w + m, 0)) || (rc = D.fetch(out1, w + m, n1 * 8)))) return rc;
+    if (out2 && ((rc = hist_launch(A, w, nbins, edges, npairs, pairs, w + m, 0)) || (rc = D.fetch(out2, w + m, n2 * 8)))) return rc;
     return 0;
 }
 

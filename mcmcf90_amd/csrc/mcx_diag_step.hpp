@@ -14,8 +14,8 @@
 // three or two up to the cap: the registers bound the occupancy, as in the identity, except at W = 1 above 318 bins (four blocks at the
 // cap).  One field a block would quarter the LDS and change nothing below that; the grid stays the identity's.
 //
-// The kernel restates diag_tile_kernel's body, as diag_xf_tile_kernel does and for the reason given there; a change to one body belongs
-// in the others.
+// The kernel restates diag_tile_kernel's body, as diag_xf_tile_kernel does and for the measured reason given there (mcx_diag_xf.hpp;
+// profiles/r20_a/summary_body_ab.txt); a change to one body belongs in the others.
 #pragma once
 #include "mcx_diag.hpp"
 #include "mcx_hist.hpp"

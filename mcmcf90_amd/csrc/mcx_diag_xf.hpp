@@ -7,10 +7,12 @@
 // places a value leaves its load -- the mean pass here and diag_block (mcx_diag.hpp) -- and a_f is read once per wave, beside the shift.
 // Kind 0 is diag_tile_kernel<W> itself and has no kernel here.  Included after mcx_quant.hpp, which owns the key map.
 //
-// diag_xf_tile_kernel restates diag_tile_kernel's body instead of sharing it: a body both kernels call receives the argument block as a
-// private copy, and diag_tile_kernel<W> then compiles to other scalar code in all four instantiations (as it does when DiagArgs is laid
-// out otherwise, mcx_diag.hpp) -- it is the definition's bits and stays the instructions it was.  Both are held to the same restatement,
-// bit for bit, by the tests; a change to one body belongs in the other.
+// diag_xf_tile_kernel restates diag_tile_kernel's body instead of sharing it, and that was measured (profiles/r20_a/summary_body_ab.txt):
+// with one body, the argument block by const reference and u a functor, all twenty tile kernels keep their registers and waves (two of
+// W = 33 lose two VGPRs) and their instruction counts within 32, but the schedules differ, and over a whole ring at W = 33 the identity
+// is slower in all six cells measured, by 0.4 - 1.2 % (70.3 -> 71.1 ms on the headline's shape), and kind 1 by 0.5 % (79.9 -> 80.3 ms);
+// the restated kernels' own two runs differ by 0.1 - 1.0 % there.  Both are held to the same restatement, bit for bit, by the tests; a
+// change to one body belongs in the other.
 #pragma once
 #include "mcx_quant.hpp"
 

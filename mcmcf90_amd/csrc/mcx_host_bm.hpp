@@ -1,7 +1,8 @@
 // mcx_host_bm.hpp -- the sample store's batch-means covariance, host side (mcmcx_samples_cov_bm / _dev, mcmcx_debug_samples_cov_bm) and
 // its two finishes, the multivariate ESS and the multivariate split-R-hat (mcmcx_samples_mess, mcmcx_samples_mpsrf): the refusals, the
-// launches of mcx_bm.hpp's kernels, and pure host arithmetic on a cov vector and a batch-means vector.  The window, the scratch, the shift
-// and the tree launch are mcx_host_samples.hpp's; the vector's layout, its scratch and its finish formulas are mcx_host_cov.hpp's.
+// launches of mcx_bm.hpp's kernels, and pure host arithmetic on a cov vector and a batch-means vector.  The window, the scratch, a reader's
+// prologue and the shift are mcx_host_samples.hpp's; the vector's layout, its scratch, the launches around the tile kernel (form, grids,
+// tree, pack) and its finish formulas are mcx_host_cov.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_cov.hpp); not a stand-alone header.
 
 // every refusal is -55, on the host, before anything is launched or allocated
@@ -15,49 +16,31 @@ static int bm_check(mcmcx_engine *h, int s0, int ns, int batch, const void *out,
     return 0;
 }
 
-// The batch-means vector of window W (scratch w of cov_scratch_len doubles) into dev_out; asynchronous on `stream`.  shift: host memory
-// or nullptr (chain 0 of window sample 0).  1 <= batch <= W.ns; the last W.ns - nb batch samples are not read.
+// The batch-means vector of window W (scratch w as cov_launch's) into dev_out; asynchronous on `stream`.  shift: host memory or nullptr
+// (chain 0 of window sample 0).  1 <= batch <= W.ns; the last W.ns - nb batch samples are not read.
 static int bm_launch(const SampleWin &W, int batch, double *w, const double *shift, double *dev_out, hipStream_t stream)
 {
-    const int nf = W.nfields, T = W.ntiles, nb = W.ns / batch;
-    const size_t len = cov_row_len(nf);
-    double *rows = w, *dshift = rows + (size_t)T * len;
+    const int nb = W.ns / batch;
+    double *rows = w, *dshift = rows + (size_t)W.ntiles * cov_row_len(W.nfields);
     int rc = samples_shift(W, shift, dshift, stream); if (rc) return rc;
     BmArgs A;
     A.store = W.store; A.shift = dshift; A.out = rows; A.slot0 = W.slot0; A.cap = W.cap;
-    A.ntiles = T; A.nfields = nf; A.nchains = W.nchains; A.ns = nb * batch; A.batch = batch;
-    const int nblk = (nf + 1 + 15) / 16;                        // 16-row blocks of the fields and the row of ones
-    const dim3 block(64);
-    if (nblk <= 4) {                                            // form A: the whole upper block triangle in one wave
-        const dim3 grid((unsigned)T);
-        if (nblk == 1) hipLaunchKernelGGL((bm_tile_kernel<1, false>), grid, block, 0, stream, A);
-        else if (nblk == 2) hipLaunchKernelGGL((bm_tile_kernel<2, false>), grid, block, 0, stream, A);
-        else if (nblk == 3) hipLaunchKernelGGL((bm_tile_kernel<3, false>), grid, block, 0, stream, A);
-        else hipLaunchKernelGGL((bm_tile_kernel<4, false>), grid, block, 0, stream, A);
-    } else {                                                    // form B: super-blocks of two, their diagonal and their pairs
-        const int nsup = (nblk + 1) / 2;
-        hipLaunchKernelGGL((bm_tile_kernel<2, false>), dim3((unsigned)T, (unsigned)nsup), block, 0, stream, A);
-        hipLaunchKernelGGL((bm_tile_kernel<4, true>), dim3((unsigned)T, (unsigned)(nsup * (nsup - 1) / 2)), block, 0, stream, A);
-    }
-    const int ilen = (int)len, vlen = (int)cov_vec_len(nf);
-    moments_tree_launch(stream, rows, T, ilen, nullptr);
-    hipLaunchKernelGGL(cov_pack_kernel, dim3((unsigned)((vlen + 255) / 256)), dim3(256), 0, stream, (const double *)rows,
-        (const double *)dshift, dev_out, nf, ilen, (double)((int64_t)nb * (int64_t)W.nchains));
-    HIPCHK(hipGetLastError());
-    return 0;
+    A.ntiles = W.ntiles; A.nfields = W.nfields; A.nchains = W.nchains; A.ns = nb * batch; A.batch = batch;
+    return cov_tiles_launch(W.nfields, W.ntiles, rows, dshift, (double)((int64_t)nb * (int64_t)W.nchains), dev_out, stream,
+        [&](auto ns, auto off, dim3 grid) {
+            hipLaunchKernelGGL((bm_tile_kernel<decltype(ns)::value, decltype(off)::value>), grid, dim3(64), 0, stream, A);
+        });
 }
 
-// the batch-means vector of the engine's window into dev_out (nullptr: the scratch's staging vector, returned in *staged)
-static int bm_engine(mcmcx_engine *h, int s0, int ns, int batch, const double *shift, double *dev_out, double **staged)
+// mcmcx_samples_cov_bm and its _dev form: the refusals, then the batch-means vector of the engine's window into dev_out or, host_out
+// given, into the scratch's staging vector and from there
+static int bm_run(mcmcx_engine *h, int s0, int ns, int batch, const double *shift, void *dev_out, double *host_out, const char *who)
 {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const SampleWin W = samples_window(h, s0, ns);
-    const size_t need = cov_scratch_len(W.ntiles, W.nfields);
-    int rc = samples_scratch(h, need * sizeof(double)); if (rc) return rc;
-    double *w = (double *)h->d_scratch;
-    if (!dev_out) dev_out = w + need - cov_vec_len(W.nfields);
-    if (staged) *staged = dev_out;
-    return bm_launch(W, batch, w, shift, dev_out, h->stream);
+    int rc = bm_check(h, s0, ns, batch, dev_out ? dev_out : host_out, who); if (rc) return rc;
+    const size_t work = cov_work_len(h->ntiles, samples_nfields(h)), vlen = cov_vec_len(samples_nfields(h));
+    return samples_run<double>(h, s0, ns, work + vlen, work, vlen, dev_out, host_out, [&](const SampleWin &W, double *w, double *out) {
+        return bm_launch(W, batch, w, shift, out, h->stream);
+    });
 }
 
 // ---- the finishes (include/mcmcx.h states them): pure host, no handle, no device

@@ -1,15 +1,13 @@
 // mcx_host_cov.hpp -- the sample store's posterior covariance, host side (mcmcx_samples_cov / _dev / _finish, mcmcx_debug_samples_cov):
-// its own refusals, its layout of the readers' scratch, the launches of mcx_cov.hpp's kernels, and the finish -- pure host arithmetic on
-// a cov vector.  The window, the scratch, the shift and the tree launch are mcx_host_samples.hpp's.
+// its own refusals, its layout of the readers' scratch, the launches of mcx_cov.hpp's kernels -- the choice of their form, the grids, the
+// tree and the pack for the batch-means covariance (mcx_host_bm.hpp) too -- and the finish, pure host arithmetic on a cov vector.  The
+// window, the scratch, a reader's prologue, the shift and the tree launch are mcx_host_samples.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_quant.hpp); not a stand-alone header.
 
 static size_t cov_row_len(int nfields) { return (size_t)nfields + (size_t)nfields * (size_t)(nfields + 1) / 2; }
 static size_t cov_vec_len(int nfields) { return 1 + (size_t)nfields + cov_row_len(nfields); }
-// doubles of the scratch: [ntiles][row] tile rows, shift[nfields], one cov vector (the host form's staging)
-static size_t cov_scratch_len(int ntiles, int nfields)
-{
-    return (size_t)ntiles * cov_row_len(nfields) + (size_t)nfields + cov_vec_len(nfields);
-}
+// doubles of the scratch before the one cov vector at its end (the host form's staging): [ntiles][row] tile rows, shift[nfields]
+static size_t cov_work_len(int ntiles, int nfields) { return (size_t)ntiles * cov_row_len(nfields) + (size_t)nfields; }
 
 // every refusal is -51, on the host, before anything is launched or allocated
 static int cov_check(mcmcx_engine *h, int s0, int ns, const void *out, const char *who)
@@ -19,50 +17,58 @@ static int cov_check(mcmcx_engine *h, int s0, int ns, const void *out, const cha
     return samples_window_check(h, s0, ns, -51, 1, who);
 }
 
-// The cov vector of window W (scratch w of cov_scratch_len doubles) into dev_out; asynchronous on `stream`.  shift: host memory or
-// nullptr (chain 0 of window sample 0).
-static int cov_launch(const SampleWin &W, double *w, const double *shift, double *dev_out, hipStream_t stream)
+// The launches of a covariance over the tiles of a store of nf fields, the batch-means covariance's too: `tile` launches the caller's
+// kernel<NS, OFF> on a grid it is handed (NS and OFF as std::integral_constant, compile-time values), then the tree over the tile rows
+// and the vector [n, shift, S, G] packed into dev_out.  Asynchronous on `stream`.
+template <class L>
+static int cov_tiles_launch(int nf, int T, double *rows, const double *dshift, double n, double *dev_out, hipStream_t stream, L &&tile)
 {
-    const int nf = W.nfields, T = W.ntiles;
-    const size_t len = cov_row_len(nf);
-    double *rows = w, *dshift = rows + (size_t)T * len;
-    int rc = samples_shift(W, shift, dshift, stream); if (rc) return rc;
-    CovArgs A;
-    A.store = W.store; A.shift = dshift; A.out = rows; A.slot0 = W.slot0; A.cap = W.cap;
-    A.ntiles = T; A.nfields = nf; A.nchains = W.nchains; A.ns = W.ns;
+    using std::integral_constant;
+    typedef integral_constant<bool, false> diag;
     const int nblk = (nf + 1 + 15) / 16;                        // 16-row blocks of the fields and the row of ones
-    const dim3 block(64);
-    if (nblk <= 4) {                                            // form A: the whole upper block triangle in one wave
-        const dim3 grid((unsigned)T);
-        if (nblk == 1) hipLaunchKernelGGL((cov_tile_kernel<1, false>), grid, block, 0, stream, A);
-        else if (nblk == 2) hipLaunchKernelGGL((cov_tile_kernel<2, false>), grid, block, 0, stream, A);
-        else if (nblk == 3) hipLaunchKernelGGL((cov_tile_kernel<3, false>), grid, block, 0, stream, A);
-        else hipLaunchKernelGGL((cov_tile_kernel<4, false>), grid, block, 0, stream, A);
-    } else {                                                    // form B: super-blocks of two, their diagonal and their pairs
+    const dim3 grid((unsigned)T);
+    if (nblk == 1) tile(integral_constant<int, 1>(), diag(), grid);     // form A: the whole upper block triangle in one wave
+    else if (nblk == 2) tile(integral_constant<int, 2>(), diag(), grid);
+    else if (nblk == 3) tile(integral_constant<int, 3>(), diag(), grid);
+    else if (nblk <= 4) tile(integral_constant<int, 4>(), diag(), grid);
+    else {                                                      // form B: super-blocks of two, their diagonal and their pairs
         const int nsup = (nblk + 1) / 2;
-        hipLaunchKernelGGL((cov_tile_kernel<2, false>), dim3((unsigned)T, (unsigned)nsup), block, 0, stream, A);
-        hipLaunchKernelGGL((cov_tile_kernel<4, true>), dim3((unsigned)T, (unsigned)(nsup * (nsup - 1) / 2)), block, 0, stream, A);
+        tile(integral_constant<int, 2>(), diag(), dim3((unsigned)T, (unsigned)nsup));
+        tile(integral_constant<int, 4>(), integral_constant<bool, true>(), dim3((unsigned)T, (unsigned)(nsup * (nsup - 1) / 2)));
     }
     // the length is a size_t at real sizes only in bytes: nfields <= 2047 keeps it an int (the store's nfields is far below)
-    const int ilen = (int)len, vlen = (int)cov_vec_len(nf);
+    const int ilen = (int)cov_row_len(nf), vlen = (int)cov_vec_len(nf);
     moments_tree_launch(stream, rows, T, ilen, nullptr);
-    hipLaunchKernelGGL(cov_pack_kernel, dim3((unsigned)((vlen + 255) / 256)), dim3(256), 0, stream, (const double *)rows,
-        (const double *)dshift, dev_out, nf, ilen, (double)((int64_t)W.ns * (int64_t)W.nchains));
+    hipLaunchKernelGGL(cov_pack_kernel, dim3((unsigned)((vlen + 255) / 256)), dim3(256), 0, stream, (const double *)rows, dshift, dev_out,
+        nf, ilen, n);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// the cov vector of the engine's window into dev_out (nullptr: the scratch's staging vector, returned in *staged)
-static int cov_engine(mcmcx_engine *h, int s0, int ns, const double *shift, double *dev_out, double **staged)
+// The cov vector of window W (scratch w: cov_work_len doubles and, where dev_out lies there, the vector) into dev_out; asynchronous on
+// `stream`.  shift: host memory or nullptr (chain 0 of window sample 0).
+static int cov_launch(const SampleWin &W, double *w, const double *shift, double *dev_out, hipStream_t stream)
 {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const SampleWin W = samples_window(h, s0, ns);
-    const size_t need = cov_scratch_len(W.ntiles, W.nfields);
-    int rc = samples_scratch(h, need * sizeof(double)); if (rc) return rc;
-    double *w = (double *)h->d_scratch;
-    if (!dev_out) dev_out = w + need - cov_vec_len(W.nfields);
-    if (staged) *staged = dev_out;
-    return cov_launch(W, w, shift, dev_out, h->stream);
+    double *rows = w, *dshift = rows + (size_t)W.ntiles * cov_row_len(W.nfields);
+    int rc = samples_shift(W, shift, dshift, stream); if (rc) return rc;
+    CovArgs A;
+    A.store = W.store; A.shift = dshift; A.out = rows; A.slot0 = W.slot0; A.cap = W.cap;
+    A.ntiles = W.ntiles; A.nfields = W.nfields; A.nchains = W.nchains; A.ns = W.ns;
+    return cov_tiles_launch(W.nfields, W.ntiles, rows, dshift, (double)((int64_t)W.ns * (int64_t)W.nchains), dev_out, stream,
+        [&](auto ns, auto off, dim3 grid) {
+            hipLaunchKernelGGL((cov_tile_kernel<decltype(ns)::value, decltype(off)::value>), grid, dim3(64), 0, stream, A);
+        });
+}
+
+// mcmcx_samples_cov and its _dev form: the refusals, then the cov vector of the engine's window into dev_out or, host_out given, into the
+// scratch's staging vector and from there
+static int cov_run(mcmcx_engine *h, int s0, int ns, const double *shift, void *dev_out, double *host_out, const char *who)
+{
+    int rc = cov_check(h, s0, ns, dev_out ? dev_out : host_out, who); if (rc) return rc;
+    const size_t work = cov_work_len(h->ntiles, samples_nfields(h)), vlen = cov_vec_len(samples_nfields(h));
+    return samples_run<double>(h, s0, ns, work + vlen, work, vlen, dev_out, host_out, [&](const SampleWin &W, double *w, double *out) {
+        return cov_launch(W, w, shift, out, h->stream);
+    });
 }
 
 // The finish (include/mcmcx.h states it): mean[nf], cov and corr column-major nf x nf (corr may be null)

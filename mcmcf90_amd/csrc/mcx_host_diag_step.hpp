@@ -1,16 +1,15 @@
 // mcx_host_diag_step.hpp -- the summary of a step function of the sample store, host side (mcmcx_samples_stats_step / _dev,
 // mcmcx_debug_samples_stats_step, mcmcx_samples_rank_scores): its own refusals, its layout of the readers' scratch, the launches of
-// mcx_diag_step.hpp's kernels, and the table of normal scores -- pure host arithmetic on histogram counts.  The window, the scratch and the
-// tree launch are mcx_host_samples.hpp's, the stats vector's length and the argument block mcx_host_diag.hpp's, the edges' rules
-// mcx_host_hist.hpp's.
+// mcx_diag_step.hpp's kernels, and the table of normal scores -- pure host arithmetic on histogram counts.  The window, the scratch, a
+// reader's prologue, the staging of keys and the tree launch are mcx_host_samples.hpp's; the stats vector's length, the argument block,
+// the choice of an instantiation by K and what follows the tile kernel mcx_host_diag.hpp's; the edges' rules mcx_host_hist.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_hist.hpp); not a stand-alone header.
 
-// doubles of the scratch: the summary's tile rows and shift[nfields], the edges' keys [nfields][nbins + 1], the table
-// [nfields][nbins + 2], one stats vector (the host form's staging)
-static size_t diag_step_scratch_len(int ntiles, int nfields, int maxlag, int nbins)
+// doubles of the scratch before the one stats vector at its end (the host form's staging): the summary's tile rows and shift[nfields],
+// the edges' keys [nfields][nbins + 1], the table [nfields][nbins + 2]
+static size_t diag_step_work_len(int ntiles, int nfields, int maxlag, int nbins)
 {
-    return (size_t)ntiles * (size_t)nfields * (size_t)(maxlag + 3) + (size_t)nfields + (size_t)nfields * (size_t)(2 * nbins + 3) +
-        (size_t)diag_stats_len(nfields, maxlag);
+    return diag_work_len(ntiles, nfields, maxlag) + (size_t)nfields * (size_t)(2 * nbins + 3);
 }
 
 // every refusal is -54, on the host, before anything is launched or allocated.  What the arguments alone decide comes first: the
@@ -35,56 +34,41 @@ static int diag_step_check(mcmcx_engine *h, int s0, int ns, int maxlag, int nbin
     return diag_check(h, s0, ns, maxlag, out, who, -54);
 }
 
-// The stats vector of u(window W) (scratch w of diag_step_scratch_len doubles) into dev_out; asynchronous on `stream`.  edges, table and
-// shift are host memory; shift == nullptr: u of chain 0 of window sample 0.
+// The stats vector of u(window W) (scratch w: diag_step_work_len doubles and, where dev_out lies there, the vector) into dev_out;
+// asynchronous on `stream`.  edges, table and shift are host memory; shift == nullptr: u of chain 0 of window sample 0.
 static int diag_step_launch(const SampleWin &W, double *w, int maxlag, int nbins, const double *edges, const double *table,
                             const double *shift, double *dev_out, hipStream_t stream)
 {
-    const int nf = W.nfields, T = W.ntiles, nh = W.ns / 2, K = std::min(maxlag, nh - 1), ne = nbins + 1, nc = nbins + 2;
-    const int len = nf * (maxlag + 3), slen = diag_stats_len(nf, maxlag);
-    double *rows = w, *dshift = rows + (size_t)T * (size_t)len;
+    const int nf = W.nfields, ne = nbins + 1, nc = nbins + 2;
+    double *rows = w, *dshift = rows + (size_t)W.ntiles * (size_t)nf * (size_t)(maxlag + 3);
     unsigned long long *dkeys = (unsigned long long *)(dshift + nf);
     double *dtable = (double *)(dkeys + (size_t)nf * (size_t)ne);
-    const size_t m = (size_t)nf * (size_t)ne;
-    std::vector<unsigned long long> keys(m);
-    for (size_t i = 0; i < m; ++i) { unsigned long long b; memcpy(&b, edges + i, 8); keys[i] = quant_key(b); }
-    // from pageable memory a copy is staged before it returns: `keys`, table and shift need only live until then
-    HIPCHK(hipMemcpyAsync(dkeys, keys.data(), m * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    int rc = samples_stage_keys(dkeys, edges, (size_t)nf * (size_t)ne, stream); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(dtable, table, (size_t)nf * (size_t)nc * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, stream));
-    else hipLaunchKernelGGL(diag_step_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, W.store,
-        (const unsigned long long *)dkeys, (const double *)dtable, dshift, W.slot0, T, nf, nbins);
-    DiagArgs A;
-    A.store = W.store; A.shift = dshift; A.out = rows; A.slot0 = W.slot0; A.cap = W.cap;
-    A.ntiles = T; A.nfields = nf; A.nchains = W.nchains; A.ns = W.ns; A.nh = nh; A.K = K; A.maxlag = maxlag;
-    const dim3 grid((unsigned)T, (unsigned)((nf + 3) / 4)), block(256);
-    const size_t lds = 4 * (size_t)(ne + nc) * sizeof(unsigned long long);
+    const DiagArgs A = diag_args(W, dshift, rows, maxlag);
     const unsigned long long *ek = dkeys;
     const double *tb = dtable;
-    // the window length W of the instantiation holds lags 0 .. W - 1 >= K
-    if (K == 0) hipLaunchKernelGGL(diag_step_tile_kernel<1>, grid, block, lds, stream, A, ek, tb, nbins);
-    else if (K <= 8) hipLaunchKernelGGL(diag_step_tile_kernel<9>, grid, block, lds, stream, A, ek, tb, nbins);
-    else if (K <= 16) hipLaunchKernelGGL(diag_step_tile_kernel<17>, grid, block, lds, stream, A, ek, tb, nbins);
-    else hipLaunchKernelGGL(diag_step_tile_kernel<33>, grid, block, lds, stream, A, ek, tb, nbins);
-    moments_tree_launch(stream, rows, T, len, nullptr);
-    hipLaunchKernelGGL(diag_pack_kernel, dim3((unsigned)((slen + 255) / 256)), dim3(256), 0, stream, (const double *)rows,
-        (const double *)dshift, dev_out, nf, maxlag, 2.0 * (double)W.nchains, (double)nh, (double)K);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, stream));
+    else hipLaunchKernelGGL(diag_step_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, W.store, ek, tb, dshift,
+        W.slot0, W.ntiles, nf, nbins);
+    const size_t lds = 4 * (size_t)(ne + nc) * sizeof(unsigned long long);
+    diag_with_W(A.K, [&](auto w_) {
+        hipLaunchKernelGGL(diag_step_tile_kernel<decltype(w_)::value>, diag_grid(A), dim3(256), lds, stream, A, ek, tb, nbins);
+    });
+    return diag_finish_launch(A, dev_out, stream);
 }
 
-// the stats vector of u(the engine's window) into dev_out (nullptr: the scratch's staging vector, returned in *staged)
-static int diag_step_engine(mcmcx_engine *h, int s0, int ns, int maxlag, int nbins, const double *edges, const double *table,
-                            const double *shift, double *dev_out, double **staged)
+// mcmcx_samples_stats_step and its _dev form: the refusals, then the stats vector of u(the engine's window) into dev_out or, host_out
+// given, into the scratch's staging vector and from there
+static int diag_step_run(mcmcx_engine *h, int s0, int ns, int maxlag, int nbins, const double *edges, const double *table,
+                         const double *shift, void *dev_out, double *host_out, const char *who)
 {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const SampleWin W = samples_window(h, s0, ns);
-    const size_t need = diag_step_scratch_len(W.ntiles, W.nfields, maxlag, nbins);
-    int rc = samples_scratch(h, need * sizeof(double)); if (rc) return rc;
-    double *w = (double *)h->d_scratch;
-    if (!dev_out) dev_out = w + need - (size_t)diag_stats_len(W.nfields, maxlag);
-    if (staged) *staged = dev_out;
-    return diag_step_launch(W, w, maxlag, nbins, edges, table, shift, dev_out, h->stream);
+    int rc = diag_step_check(h, s0, ns, maxlag, nbins, edges, table, dev_out ? dev_out : host_out, who); if (rc) return rc;
+    const int nf = samples_nfields(h);
+    const size_t work = diag_step_work_len(h->ntiles, nf, maxlag, nbins), slen = (size_t)diag_stats_len(nf, maxlag);
+    return samples_run<double>(h, s0, ns, work + slen, work, slen, dev_out, host_out, [&](const SampleWin &W, double *w, double *out) {
+        return diag_step_launch(W, w, maxlag, nbins, edges, table, shift, out, h->stream);
+    });
 }
 
 // Phi^-1(p) for 0 < p < 1: Wichura's algorithm AS241 (Applied Statistics 37, 1988), routine PPND16, operation by operation -- three

@@ -1,6 +1,7 @@
 // mcx_host_hist.hpp -- marginal and pairwise joint histograms of the sample store, host side (mcmcx_samples_hist / _hist2 / _hist_edges /
 // _hist_density, mcmcx_debug_samples_hist): its own refusals, its layout of the readers' scratch, the launches of mcx_hist.hpp's kernels,
-// the uniform edges and the density finish -- pure host arithmetic.  The window and the scratch are mcx_host_samples.hpp's.
+// the uniform edges and the density finish -- pure host arithmetic.  The window, the scratch, a reader's prologue and the staging of keys
+// are mcx_host_samples.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_quant.hpp); not a stand-alone header.
 
 // every refusal is -52, on the host, before anything is launched or allocated.  What the arguments alone decide comes first, so that it
@@ -88,11 +89,8 @@ static int hist_launch(const QuantWin &A, unsigned long long *wkeys, int nbins, 
                        unsigned long long *dev_out, hipStream_t stream)
 {
     const int nf = A.win.nfields, T = A.win.ntiles, ne = nbins + 1, nc = nbins + 2, ny = npairs ? npairs : nf;
-    const size_t m = hist_key_words(nf, nbins), words = hist_table_words(nf, npairs, nbins);
-    std::vector<unsigned long long> keys(m);
-    for (size_t i = 0; i < m; ++i) { unsigned long long b; memcpy(&b, edges + i, 8); keys[i] = quant_key(b); }
-    // from pageable memory the copy is staged before it returns: `keys` and edges need only live until then
-    HIPCHK(hipMemcpyAsync(wkeys, keys.data(), m * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    const size_t words = hist_table_words(nf, npairs, nbins);
+    int rc = samples_stage_keys(wkeys, edges, hist_key_words(nf, nbins), stream); if (rc) return rc;
     int top = 1;
     while (2 * top <= ne) top *= 2;
     const long long t4 = ((long long)T + 3) / 4;
@@ -113,19 +111,17 @@ static int hist_launch(const QuantWin &A, unsigned long long *wkeys, int nbins, 
     return 0;
 }
 
-// the table of the engine's window into dev_out (nullptr: the scratch's own staging table, returned in *staged); the scratch holds the
-// edges' keys, then that table
-static int hist_engine(mcmcx_engine *h, int s0, int ns, int nbins, const double *edges, int npairs, const int32_t *pairs,
-                       unsigned long long *dev_out, unsigned long long **staged)
+// mcmcx_samples_hist, _hist2 (two: npairs pairs) and their _dev forms: the refusals, then the table of the engine's window into dev_out
+// or, host_out given, into the scratch's staging table and from there; the scratch holds the edges' keys, then that table
+static int hist_run(mcmcx_engine *h, int s0, int ns, bool two, int npairs, const int32_t *pairs, int nbins, const double *edges,
+                    void *dev_out, int64_t *host_out, const char *who)
 {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const int nf = samples_nfields(h);
-    const size_t m = hist_key_words(nf, nbins);
-    int rc = samples_scratch(h, (m + hist_table_words(nf, npairs, nbins)) * sizeof(unsigned long long)); if (rc) return rc;
-    unsigned long long *w = (unsigned long long *)h->d_scratch;
-    if (!dev_out) dev_out = w + m;
-    if (staged) *staged = dev_out;
-    return hist_launch(hist_window(samples_window(h, s0, ns), 0), w, nbins, edges, npairs, pairs, dev_out, h->stream);
+    int rc = hist_check(h, s0, ns, two, npairs, pairs, nbins, edges, dev_out ? dev_out : host_out, who); if (rc) return rc;
+    const size_t m = hist_key_words(samples_nfields(h), nbins), words = hist_table_words(samples_nfields(h), npairs, nbins);
+    typedef unsigned long long u64;
+    return samples_run<u64>(h, s0, ns, m + words, m, words, dev_out, host_out, [&](const SampleWin &W, u64 *w, u64 *out) {
+        return hist_launch(hist_window(W, 0), w, nbins, edges, npairs, pairs, out, h->stream);
+    });
 }
 
 // e_i = lo + (hi - lo) * ((double)i / nbins) for i < nbins, e_nbins = hi

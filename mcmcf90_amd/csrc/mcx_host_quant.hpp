@@ -1,6 +1,6 @@
 // mcx_host_quant.hpp -- exact order statistics, tail counts and quantiles of the sample store, host side (mcmcx_samples_order_stats /
 // _counts / _quantile_ranks / _quantiles): its own refusals, its layouts of the readers' scratch, the launches of mcx_quant.hpp's kernels,
-// the quantile's finish.  The window and the scratch are mcx_host_samples.hpp's.
+// the quantile's finish.  The window, the scratch, a reader's prologue and the staging of keys are mcx_host_samples.hpp's.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_diag.hpp); not a stand-alone header.
 
 // every refusal is -50, on the host, before anything is launched or allocated (nr: the number of ranks or thresholds).  What the
@@ -23,9 +23,8 @@ static int quant_check_ranks(long long n, int nr, const int64_t *ranks, const ch
     return 0;
 }
 
-// 64-bit words of a select's scratch (table, prefix, rest, leader, the host form's staging vector) and of a counts call's (counts, keys)
+// 64-bit words of a select's scratch (table, prefix, rest, leader, the host form's staging vector)
 static size_t quant_select_words(int nf, int nr) { return (size_t)nf * (size_t)nr * (size_t)(QUANT_NB + 4); }
-static size_t quant_counts_words(int nf, int nq) { return (size_t)nf * (size_t)nq * 3; }
 
 static QuantWin quant_window(const SampleWin &W)
 {
@@ -59,42 +58,50 @@ static int quant_select_launch(const QuantWin &A, unsigned long long *w, int nr,
     return 0;
 }
 
-static int quant_order_stats(mcmcx_engine *h, int s0, int ns, int nr, const int64_t *ranks, double *dev_out, double **staged)
+// mcmcx_samples_order_stats and its _dev form: the refusals, then the select into dev_out or, host_out given, into the scratch's
+// staging vector (the last nfields * nr words of quant_select_words) and from there
+static int quant_order_stats_run(mcmcx_engine *h, int s0, int ns, int nr, const int64_t *ranks, void *dev_out, double *host_out,
+                                 const char *who)
 {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const int nf = samples_nfields(h);
-    int rc = samples_scratch(h, quant_select_words(nf, nr) * sizeof(unsigned long long)); if (rc) return rc;
-    unsigned long long *w = (unsigned long long *)h->d_scratch;
-    if (!dev_out) dev_out = (double *)(w + (size_t)nf * (size_t)nr * (size_t)(QUANT_NB + 3));
-    if (staged) *staged = dev_out;
-    return quant_select_launch(quant_window(samples_window(h, s0, ns)), w, nr, ranks, dev_out, h->stream);
+    int rc = quant_check(h, s0, ns, nr, ranks, dev_out ? dev_out : host_out, who); if (rc) return rc;
+    if ((rc = quant_check_ranks((long long)ns * h->cfg.nchains, nr, ranks, who))) return rc;
+    const size_t m = (size_t)samples_nfields(h) * (size_t)nr, need = quant_select_words(samples_nfields(h), nr);
+    typedef unsigned long long u64;
+    return samples_run<u64>(h, s0, ns, need, need - m, m, dev_out, host_out, [&](const SampleWin &W, u64 *w, u64 *out) {
+        return quant_select_launch(quant_window(W), w, nr, ranks, (double *)out, h->stream);
+    });
 }
 
-// lt / le of nq thresholds per field (x[nfields][nq], host) into dev_out[nfields][nq][2] (nullptr: the scratch's own); asynchronous
-static int quant_counts(mcmcx_engine *h, int s0, int ns, int nq, const double *x, unsigned long long *dev_out, unsigned long long **staged)
+// lt / le of nq thresholds per field (x[nfields][nq], host) over window A into dev_out[nfields][nq][2], the thresholds' keys staged in
+// xkey; asynchronous on `stream`
+static int quant_counts_launch(const QuantWin &A, unsigned long long *xkey, int nq, const double *x, unsigned long long *dev_out,
+                               hipStream_t stream)
 {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const int nf = samples_nfields(h), T = h->ntiles;
+    const int nf = A.win.nfields, T = A.win.ntiles;
     const size_t m = (size_t)nf * (size_t)nq;
-    int rc = samples_scratch(h, quant_counts_words(nf, nq) * sizeof(unsigned long long)); if (rc) return rc;
-    unsigned long long *w = (unsigned long long *)h->d_scratch, *xkey = w + 2 * m;
-    if (!dev_out) dev_out = w;
-    if (staged) *staged = dev_out;
-    std::vector<unsigned long long> keys(m);
-    for (size_t i = 0; i < m; ++i) { unsigned long long b; memcpy(&b, x + i, 8); keys[i] = quant_key(b); }
-    // from pageable memory the copy is staged before it returns: `keys` and x need only live until then
-    HIPCHK(hipMemcpyAsync(xkey, keys.data(), m * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
-    const QuantWin A = quant_window(samples_window(h, s0, ns));
+    int rc = samples_stage_keys(xkey, x, m, stream); if (rc) return rc;
     const int fb = (nf + 3) / 4;
     const long long gx = std::min<long long>(T, std::max<long long>(std::max(1, 2560 / fb), ((long long)T + 32767) / 32768));
-    const dim3 grid((unsigned)gx, (unsigned)fb, (unsigned)((ns + A.chunk - 1) / A.chunk)), block(256);
-    hipLaunchKernelGGL(quant_counts_zero_kernel, dim3((unsigned)((2 * m + 255) / 256)), block, 0, h->stream, dev_out, (int)(2 * m));
+    const dim3 grid((unsigned)gx, (unsigned)fb, (unsigned)((A.win.ns + A.chunk - 1) / A.chunk)), block(256);
+    hipLaunchKernelGGL(quant_counts_zero_kernel, dim3((unsigned)((2 * m + 255) / 256)), block, 0, stream, dev_out, (int)(2 * m));
     const unsigned long long *xk = xkey;
-    if (nq <= 2) hipLaunchKernelGGL(quant_counts_kernel<2>, grid, block, 0, h->stream, A, xk, dev_out, nq);
-    else if (nq <= 8) hipLaunchKernelGGL(quant_counts_kernel<8>, grid, block, 0, h->stream, A, xk, dev_out, nq);
-    else hipLaunchKernelGGL(quant_counts_kernel<32>, grid, block, 0, h->stream, A, xk, dev_out, nq);
+    if (nq <= 2) hipLaunchKernelGGL(quant_counts_kernel<2>, grid, block, 0, stream, A, xk, dev_out, nq);
+    else if (nq <= 8) hipLaunchKernelGGL(quant_counts_kernel<8>, grid, block, 0, stream, A, xk, dev_out, nq);
+    else hipLaunchKernelGGL(quant_counts_kernel<32>, grid, block, 0, stream, A, xk, dev_out, nq);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// mcmcx_samples_counts and its _dev form: the refusals, then the counts into dev_out or, host_out given, into the scratch's own (its
+// first 2 nfields nq words; the keys lie behind them) and from there
+static int quant_counts_run(mcmcx_engine *h, int s0, int ns, int nq, const double *x, void *dev_out, int64_t *host_out, const char *who)
+{
+    int rc = quant_check(h, s0, ns, nq, x, dev_out ? dev_out : host_out, who); if (rc) return rc;
+    const size_t m2 = (size_t)samples_nfields(h) * (size_t)nq * 2;
+    typedef unsigned long long u64;
+    return samples_run<u64>(h, s0, ns, m2 + m2 / 2, 0, m2, dev_out, host_out, [&](const SampleWin &W, u64 *w, u64 *out) {
+        return quant_counts_launch(quant_window(W), w + m2, nq, x, out, h->stream);
+    });
 }
 
 // Hyndman-Fan type 7: pos = p (n - 1), lo = floor(pos), hi = min(lo + 1, n - 1), g = pos - lo

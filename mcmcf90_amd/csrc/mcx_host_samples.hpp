@@ -1,7 +1,8 @@
 // mcx_host_samples.hpp -- the thinned sample store's host side (mcmcx_set_samples): the rule, the store's allocation, the keep between two
 // launches, the window checks and launches of the two read kernels (mcx_samples.hpp) -- and what every reader of the ring shares
-// (mcx_host_diag.hpp, mcx_host_quant.hpp, mcx_host_cov.hpp): the window as a launch argument, its refusals, the one scratch, the default
-// shift, the launch of the pooled moment tree and the host form of a staged result.
+// (mcx_host_diag.hpp, mcx_host_quant.hpp, mcx_host_hist.hpp, mcx_host_diag_step.hpp, mcx_host_cov.hpp, mcx_host_bm.hpp): the window as a
+// launch argument, its refusals, the one scratch, a reader's prologue, the default shift, the staging of keys, the launch of the pooled
+// moment tree, the host form of a staged result and the debug probes' own store.
 // Part of the ONE translation unit mcx_api.hip (included there after mcx_host_launch.hpp); not a stand-alone header.
 
 // Iteration it is kept: a function of the configuration alone -- the same on every rank, no collective behind it.  thin = 0: never.
@@ -113,6 +114,28 @@ static int samples_scratch(mcmcx_engine *h, size_t bytes)
     return 0;
 }
 
+// the host form of a result a launch left in device memory at `staged`
+static int samples_fetch(mcmcx_engine *h, void *host_out, const void *staged, size_t bytes)
+{
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(host_out, staged, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// What every reader's entry does once its refusals are past: the device, the window, the scratch grown to `need` words of T, the reader's
+// launch(window, scratch, out) with out the caller's dev_out or, host_out given (a host form: dev_out is null), the staging area the
+// reader names -- `len` words at word stage_at of its layout -- and then the staged result to the host.
+template <class T, class L>
+static int samples_run(mcmcx_engine *h, int s0, int ns, size_t need, size_t stage_at, size_t len, void *dev_out, void *host_out, L &&launch)
+{
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const SampleWin W = samples_window(h, s0, ns);
+    int rc = samples_scratch(h, need * sizeof(T)); if (rc) return rc;
+    T *w = (T *)h->d_scratch, *out = dev_out ? (T *)dev_out : w + stage_at;
+    if ((rc = launch(W, w, out)) || !host_out) return rc;
+    return samples_fetch(h, host_out, out, len * sizeof(T));
+}
+
 // shift[nfields] of a reduction into dshift: the caller's (host memory) or, shift == nullptr, chain 0 of window sample 0
 static int samples_shift(const SampleWin &W, const double *shift, double *dshift, hipStream_t stream)
 {
@@ -120,6 +143,16 @@ static int samples_shift(const SampleWin &W, const double *shift, double *dshift
     if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, stream));
     else hipLaunchKernelGGL(diag_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, W.store, dshift, W.slot0, W.ntiles,
         nf);
+    return 0;
+}
+
+// dst[i] = quant_key(the bits of src[i]) (src: host memory, edges or thresholds), asynchronous on `stream`.  From pageable memory a copy is
+// staged before it returns: the keys here, and whatever else a reader copies up from a caller's array, need only live until then.
+static int samples_stage_keys(unsigned long long *dst, const double *src, size_t count, hipStream_t stream)
+{
+    std::vector<unsigned long long> keys(count);
+    for (size_t i = 0; i < count; ++i) { unsigned long long b; memcpy(&b, src + i, 8); keys[i] = quant_key(b); }
+    HIPCHK(hipMemcpyAsync(dst, keys.data(), count * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
     return 0;
 }
 
@@ -135,10 +168,40 @@ static void moments_tree_launch(hipStream_t stream, double *rows, int T, int len
     }
 }
 
-// the host form of a result a launch left in device memory at `staged`
-static int samples_fetch(mcmcx_engine *h, void *host_out, const void *staged, size_t bytes)
-{
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(host_out, staged, bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
+// A debug probe's own store (mcmcx_debug_samples_*; tests only): ns slots of ceil(nchains / 64) tiles and nfields fields filled from
+// values[ns][nfields][nchains] through samples_row, the padding lanes of the last tile NaN -- which a kernel that did not mask them would
+// sum, count or spread --, and a scratch of the reader's own layout beside it.  The probes work on stream 0; both buffers are freed
+// with the struct.
+struct DebugStore {
+    DevBufs g;
+    SampleWin win;
+    void *scratch = nullptr;
+
+    int open(int device, int nchains, int nfields, int ns, const double *values, size_t scratch_bytes)
+    {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+        HIPCHK(hipSetDevice(device));
+        const int T = (nchains + 63) / 64;
+        const size_t words = (size_t)ns * (size_t)T * (size_t)nfields * 64;
+        std::vector<double> host(words, std::nan(""));
+        for (int s = 0; s < ns; ++s)
+            for (int f = 0; f < nfields; ++f)
+                for (int c = 0; c < nchains; ++c)
+                    host[samples_row((size_t)s, (size_t)T, (size_t)nfields, (size_t)(c / 64), (size_t)f) + (size_t)(c % 64)] =
+                        values[((size_t)s * (size_t)nfields + (size_t)f) * (size_t)nchains + (size_t)c];
+        double *store = nullptr;
+        HIPCHK(g.alloc(&store, words * 8)); HIPCHK(g.alloc(&scratch, scratch_bytes));
+        HIPCHK(hipMemcpy(store, host.data(), words * 8, hipMemcpyHostToDevice));
+        win = {store, 0, (size_t)ns, T, nfields, nchains, ns};
+        return 0;
+    }
+
+    // what a launch on stream 0 left at `src`, to the host
+    int fetch(void *out, const void *src, size_t bytes)
+    {
+        HIPCHK(hipStreamSynchronize(0));
+        HIPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
