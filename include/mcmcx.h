@@ -700,6 +700,20 @@ int mcmcx_debug_samples_stats(int32_t device, int32_t nchains, int32_t nfields, 
  * nfields < 1, ns < 4, maxlag out of range. */
 int mcmcx_debug_samples_stats_step(int32_t device, int32_t nchains, int32_t nfields, int32_t ns, const double *values, int32_t maxlag,
                                    int32_t nbins, const double *edges, const double *table, const double *shift, double *out);
+/* The adaptation's singular value decomposition on a caller's matrices (no counterpart in the reference; tests only), in each of the
+ * engine's three statements of the pinned one-sided Jacobi routine: form 0 the host's (the shared initial factor; no device is
+ * touched), form 1 the lane form (one lane per matrix, the matrices interleaved into tiles of 64 as the engine stores them; lanes
+ * past nmat and lanes with need == 0 are inactive), form 2 the blocked kernels (npar 48 .. 256), chosen and launched by the very
+ * functions the adaptation tick calls, with nmat as its number of chains.  A run feeds these routines covariances of smooth chains
+ * only; this can feed zeros, ties, rank-deficient, ill-scaled and non-finite matrices, and neighbours that converge in different
+ * sweeps.  A: [nmat][d * d] column-major symmetric, host; need: [nmat] host, 0 = leave this matrix out, or NULL = all.
+ * V_out[nmat][d * d] takes the singular vectors (columns), s_out[nmat][d] the singular values, descending; rows of matrices with
+ * need == 0 are left as the caller filled them, in sweeps_out too.  sweeps_out: [nmat] or NULL, the number of sweeps in which the
+ * matrix rotated (60 at the cap: the routine's return value).  forms: NULL, or a buffer of len bytes for the names of what ran:
+ * "host_symsvd", "symsvd_dev", or the blocked form's two kernel instances joined by "+".  Refusals are -1, decided before a device
+ * is looked for: a null A, V_out or s_out, d < 1, nmat < 1, an unknown form, form 2 outside npar 48 .. 256, a len too small. */
+int mcmcx_debug_symsvd(int32_t device, int32_t form, int32_t d, int32_t nmat, const double *A, const uint8_t *need, double *V_out,
+                       double *s_out, int32_t *sweeps_out, char *forms, int32_t len);
 /* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
  * inverse != 0 the bits whose key x's bits are.  Needs no device. */
 int64_t mcmcx_debug_quant_key(double x, int32_t inverse);

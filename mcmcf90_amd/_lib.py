@@ -158,6 +158,9 @@ SYMBOLS["mcmcx_samples_stats_step_dev"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_
 SYMBOLS["mcmcx_debug_samples_stats_step"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP,
                                                         _DP])
 SYMBOLS["mcmcx_samples_rank_scores"] = (C.c_int, [_LP, C.c_int32, C.c_int32, _DP])
+# the adaptation's SVD on a caller's matrices: the host's, the lane form, the blocked kernels (tests)
+SYMBOLS["mcmcx_debug_symsvd"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.POINTER(C.c_uint8), _DP, _DP, _IP, C.c_char_p,
+                                            C.c_int32])
 
 _lib = None
 

@@ -1489,6 +1489,91 @@ int mcmcx_debug_samples_hist(int32_t device, int32_t nchains, int32_t nfields, i
     return 0;
 }
 
+// The three statements of the pinned SVD (oracle/mcx_svd.h) on a caller's matrices: form 0 host_symsvd (no device), form 1 symsvd_dev one
+// lane per matrix on tiles of 64, form 2 the blocked kernels through plan_svd and launch_svd -- what launch_adapt runs, nothing restated.
+int mcmcx_debug_symsvd(int32_t device, int32_t form, int32_t d, int32_t nmat, const double *A, const uint8_t *need, double *V_out,
+                       double *s_out, int32_t *sweeps_out, char *forms, int32_t len)
+{
+    const char *who = "mcmcx_debug_symsvd";
+    if (!A || !V_out || !s_out) return fail(-1, std::string(who) + ": null argument");
+    if (d < 1 || d > 4096) return fail(-1, std::string(who) + ": d outside 1 .. 4096");
+    if (nmat < 1) return fail(-1, std::string(who) + ": nmat < 1");
+    if (form < 0 || form > 2) return fail(-1, std::string(who) + ": form " + std::to_string(form) + " outside 0 .. 2");
+    if (form == 2 && (d < SVD_BLOCKED_MIN || d > SVD_BLOCKED_MAX)) return fail(-1, std::string(who) + ": the blocked form covers npar " +
+        std::to_string(SVD_BLOCKED_MIN) + " .. " + std::to_string(SVD_BLOCKED_MAX));
+    const SvdPlan sp = form == 2 ? plan_svd(d, nmat) : SvdPlan();
+    const std::string names = form == 0 ? "host_symsvd" : form == 1 ? "symsvd_dev" : std::string(sp.sweep_name) + "+" + sp.applyv_name;
+    if (forms && (len < 1 || (size_t)len <= names.size())) return fail(-1, std::string(who) + ": len too small for \"" + names + "\"");
+    const size_t DD = (size_t)d * d;
+    std::vector<uint8_t> nd(nmat, 1);
+    if (need) for (int m = 0; m < nmat; ++m) nd[m] = need[m] ? 1 : 0;
+    if (form == 0) {
+        std::vector<double> G, V, sv;
+        for (int m = 0; m < nmat; ++m) {
+            if (!nd[m]) continue;
+            G.assign(A + (size_t)m * DD, A + (size_t)(m + 1) * DD);
+            const int sw = host_symsvd(d, G, V, sv);
+            std::copy(V.begin(), V.end(), V_out + (size_t)m * DD); std::copy(sv.begin(), sv.end(), s_out + (size_t)m * d);
+            if (sweeps_out) sweeps_out[m] = sw;
+        }
+        if (forms) snprintf(forms, (size_t)len, "%s", names.c_str());
+        return 0;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(-10, "no HIP device: the mcmcx engine has no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    DevBufs g;
+    uint8_t *dneed = nullptr;
+    std::vector<int32_t> sw(nmat, 0);
+    if (form == 1) {
+        const int T = (nmat + 63) / 64;
+        std::vector<double> Gt((size_t)T * DD * 64, 0.0), st((size_t)T * d * 64);
+        for (int m = 0; m < nmat; ++m)
+            for (size_t e = 0; e < DD; ++e) Gt[((size_t)(m / 64) * DD + e) * 64 + m % 64] = A[(size_t)m * DD + e];
+        double *dG = nullptr, *dV = nullptr, *ds = nullptr; int *dsw = nullptr;
+        HIPCHK(g.alloc(&dG, Gt.size() * 8)); HIPCHK(g.alloc(&dV, Gt.size() * 8)); HIPCHK(g.alloc(&ds, st.size() * 8));
+        HIPCHK(g.alloc(&dsw, (size_t)nmat * sizeof(int))); HIPCHK(g.alloc(&dneed, (size_t)nmat));
+        HIPCHK(hipMemcpy(dG, Gt.data(), Gt.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(dV, 0, Gt.size() * 8)); HIPCHK(hipMemset(ds, 0, st.size() * 8));
+        HIPCHK(hipMemset(dsw, 0, (size_t)nmat * sizeof(int)));
+        HIPCHK(hipMemcpy(dneed, nd.data(), (size_t)nmat, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(debug_symsvd_kernel, dim3(T), dim3(64), 0, 0, dG, dV, ds, dsw, (const uint8_t *)dneed, nmat, d);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(Gt.data(), dV, Gt.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(st.data(), ds, st.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(sw.data(), dsw, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost));
+        for (int m = 0; m < nmat; ++m) {
+            if (!nd[m]) continue;
+            for (size_t e = 0; e < DD; ++e) V_out[(size_t)m * DD + e] = Gt[((size_t)(m / 64) * DD + e) * 64 + m % 64];
+            for (int j = 0; j < d; ++j) s_out[(size_t)m * d + j] = st[((size_t)(m / 64) * d + j) * 64 + m % 64];
+        }
+    } else {
+        double *dG = nullptr, *dV = nullptr, *ds = nullptr; mcx_d2 *rot = nullptr; uint8_t *state = nullptr; int *anyrot = nullptr;
+        const size_t npairs = std::max<size_t>((size_t)d * (d - 1) / 2, 1);
+        HIPCHK(g.alloc(&dG, (size_t)nmat * DD * 8)); HIPCHK(g.alloc(&dV, (size_t)nmat * DD * 8));
+        HIPCHK(g.alloc(&ds, (size_t)nmat * d * 8));
+        HIPCHK(g.alloc(&rot, (size_t)nmat * npairs * sizeof(mcx_d2))); HIPCHK(g.alloc(&state, (size_t)nmat));
+        HIPCHK(g.alloc(&dneed, (size_t)nmat)); HIPCHK(g.alloc(&anyrot, sizeof(int)));
+        HIPCHK(hipMemcpy(dG, A, (size_t)nmat * DD * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dneed, nd.data(), (size_t)nmat, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(state, 0, (size_t)nmat)); HIPCHK(hipMemset(ds, 0, (size_t)nmat * d * 8));
+        launch_svd(sp, 0, dG, dV, ds, rot, state, dneed, anyrot, nmat, d, sw.data());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+        std::vector<double> Vh((size_t)nmat * DD), sh((size_t)nmat * d);
+        HIPCHK(hipMemcpy(Vh.data(), dG, Vh.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(sh.data(), ds, sh.size() * 8, hipMemcpyDeviceToHost));
+        for (int m = 0; m < nmat; ++m) {
+            if (!nd[m]) continue;
+            std::copy(Vh.begin() + (size_t)m * DD, Vh.begin() + (size_t)(m + 1) * DD, V_out + (size_t)m * DD);
+            std::copy(sh.begin() + (size_t)m * d, sh.begin() + (size_t)(m + 1) * d, s_out + (size_t)m * d);
+        }
+    }
+    if (sweeps_out) for (int m = 0; m < nmat; ++m) if (nd[m]) sweeps_out[m] = sw[m];
+    if (forms) snprintf(forms, (size_t)len, "%s", names.c_str());
+    return 0;
+}
+
 int mcmcx_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out)
 {
     if (n < 1 || !a || !out) return fail(-1, "bad argument");

@@ -2,6 +2,35 @@
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch,
 // mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
+// The blocked SVD's launch sequence (mcx_svd.hpp) on chain-major arrays, in plain arguments: launch_adapt runs it on the engine's buffers,
+// mcmcx_debug_symsvd on a caller's matrices -- one statement of the sweep loop, its stop and the forms the plan names.  Gc: in the
+// matrices, out the sorted singular vectors; Vc, rot (the rotation log, d (d - 1) / 2 entries per chain), state, anyrot: scratch; svc: out
+// the singular values.  sweeps (host, [nlanes], may be null; tests): += 1 for every sweep a chain rotated in -- what the routine returns
+// (oracle/mcx_svd.h) -- read from `state` after each sweep, where 1 means "rotated in the sweep just run".
+static void launch_svd(const SvdPlan &a, hipStream_t stream, double *Gc, double *Vc, double *svc, mcx_d2 *rot, uint8_t *state,
+                       const uint8_t *need, int *anyrot, int nlanes, int d, int32_t *sweeps = nullptr)
+{
+    const dim3 L(nlanes), b64(64), b256(256);
+    std::vector<uint8_t> st(sweeps ? (size_t)nlanes : 0);
+    hipLaunchKernelGGL(svd_init_kernel, L, b256, 0, stream, Vc, state, need, nlanes, d);
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        (void)hipMemsetAsync(anyrot, 0, sizeof(int), stream);
+        // the sweep: every later column streamed past a block's pair-lanes through an LDS ring (mcx_svd.hpp); then the log replayed on V
+        if (!a.sweep32) hipLaunchKernelGGL(a.sweep, L, b256, a.sweep_lds, stream, Gc, rot, state, anyrot, nlanes, d, a.svd_sb);
+        else if (!MCX_VARIANT_SVD_SWEEP(stream, Gc, rot, state, anyrot, nlanes, d, a.sweep_lds)) hipLaunchKernelGGL(a.sweep32, L, b256,
+            a.sweep_lds, stream, Gc, rot, state, anyrot, nlanes, d);
+        hipLaunchKernelGGL(a.applyv, dim3(a.applyv_grid), b64, a.applyv_lds, stream, Vc, (const mcx_d2 *)rot, state, nlanes, d);
+        int any = 0;
+        // (reported by the caller's hipGetLastError)
+        if (hipMemcpyAsync(&any, anyrot, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess
+            || (sweeps && hipMemcpyAsync(st.data(), state, (size_t)nlanes, hipMemcpyDeviceToHost, stream) != hipSuccess)
+            || hipStreamSynchronize(stream) != hipSuccess) break;
+        if (sweeps) for (int c = 0; c < nlanes; ++c) sweeps[c] += st[c] == 1;
+        if (!any) break;
+    }
+    hipLaunchKernelGGL(svd_finish_kernel, L, b256, 0, stream, Gc, Vc, svc, state, nlanes, d);
+}
+
 // Reads the plan (KernelPlan::adapt: the geometry and the kernel instantiations, chosen at mcmcx_init), it and mode -- nothing is
 // decided here but what the tick's mode decides.
 static void launch_adapt(mcmcx_engine *h, int it, int mode)
@@ -33,26 +62,10 @@ static void launch_adapt(mcmcx_engine *h, int it, int mode)
     // large npar with an SVD factor: the factorisation runs one workgroup per chain on chain-major copies, one launch
     // pair per Jacobi sweep (the rotation log lives in Gw, which is free between tile2chain and the next tick)
     const size_t DD = (size_t)h->d * h->d;
-    const dim3 L(h->nlanes), tg((unsigned)((DD + 63) / 64), (unsigned)h->ntiles), tg1((unsigned)((h->d + 63) / 64), (unsigned)h->ntiles);
+    const dim3 tg((unsigned)((DD + 63) / 64), (unsigned)h->ntiles), tg1((unsigned)((h->d + 63) / 64), (unsigned)h->ntiles);
     hipLaunchKernelGGL(a.post, T, b64, a.post_lds, h->stream, h->E, it, mode, 1, h->d_need, batch_done);
     hipLaunchKernelGGL(tile2chain_kernel, tg, b256, 0, h->stream, h->E.Gw, h->d_Gc, DD, DD, h->d_need);
-    hipLaunchKernelGGL(svd_init_kernel, L, b256, 0, h->stream, h->d_Vc, h->d_state, h->d_need, h->nlanes, h->d);
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        (void)hipMemsetAsync(h->d_anyrot, 0, sizeof(int), h->stream);
-        // the sweep: every later column streamed past a block's pair-lanes through an LDS ring (mcx_svd.hpp); then the log replayed on V
-        if (!a.sweep32) hipLaunchKernelGGL(a.sweep, L, b256, a.sweep_lds, h->stream, h->d_Gc, (mcx_d2 *)h->E.Gw, h->d_state, h->d_anyrot,
-            h->nlanes, h->d, a.svd_sb);
-        else if (!MCX_VARIANT_SVD_SWEEP(h, a.sweep_lds)) hipLaunchKernelGGL(a.sweep32, L, b256, a.sweep_lds, h->stream, h->d_Gc,
-            (mcx_d2 *)h->E.Gw, h->d_state, h->d_anyrot, h->nlanes, h->d);
-        hipLaunchKernelGGL(a.applyv, dim3(a.applyv_grid), b64, a.applyv_lds, h->stream, h->d_Vc, (const mcx_d2 *)h->E.Gw, h->d_state,
-            h->nlanes, h->d);
-        int any = 0;
-        // (reported by the caller's hipGetLastError)
-        if (hipMemcpyAsync(&any, h->d_anyrot, sizeof(int), hipMemcpyDeviceToHost,
-            h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) break;
-        if (!any) break;
-    }
-    hipLaunchKernelGGL(svd_finish_kernel, L, b256, 0, h->stream, h->d_Gc, h->d_Vc, h->d_svc, h->d_state, h->nlanes, h->d);
+    launch_svd(a.svd, h->stream, h->d_Gc, h->d_Vc, h->d_svc, (mcx_d2 *)h->E.Gw, h->d_state, h->d_need, h->d_anyrot, h->nlanes, h->d);
     hipLaunchKernelGGL(chain2tile_kernel, tg, b256, 0, h->stream, h->d_Gc, h->E.Vw, DD, DD, h->d_need);
     hipLaunchKernelGGL(chain2tile_kernel, tg1, b256, 0, h->stream, h->d_svc, h->E.cs, (size_t)h->d, (size_t)2 * h->d, h->d_need);
     hipLaunchKernelGGL(a.post, T, b64, a.post_lds, h->stream, h->E, it, mode, 2, h->d_need, batch_done);

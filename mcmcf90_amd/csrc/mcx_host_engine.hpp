@@ -48,18 +48,24 @@ enum SharedLayout { SH_R = 1, SH_RT = 2, SH_DR = 4, SH_DRT = 8, SH_U = 16, SH_UR
 struct KernelEntry;
 // The adaptation tick's forms (launch_adapt, mcx_host_adapt.hpp): everything about its launches that npar, the tile count and the plan's
 // switches decide -- the kernels as pointers to the chosen instantiations, so that the tick compares nothing.
+// The blocked SVD's forms (plan_svd, a function of npar and the chain count; launch_svd runs them): the sweep with all 32 lanes of a row
+// group on pairs up to npar 200 (svd_sweep_stream32_kernel<RL>), 24 pair-lanes (svd_sb) and a wave of loaders above
+// (svd_sweep_stream_kernel<RL>); the log replayed on V (svd_applyv_stream32_kernel<RP>).  The names are the instances', for
+// mcmcx_debug_symsvd.
+struct SvdPlan {
+    void (*sweep32)(double *, mcx_d2 *, uint8_t *, int *, int, int) = nullptr;
+    void (*sweep)(double *, mcx_d2 *, uint8_t *, int *, int, int, int) = nullptr; int svd_sb = 0;
+    size_t sweep_lds = 0;
+    void (*applyv)(double *, const mcx_d2 *, const uint8_t *, int, int) = nullptr; unsigned applyv_grid = 0; size_t applyv_lds = 0;
+    const char *sweep_name = "", *applyv_name = "";
+};
 struct AdaptPlan {
     int n10 = 0, noff = 0; unsigned g8 = 0;            // the covariance's cover in blocks of TD: diagonal, off-diagonal, the grid's base
     // adapt_post_kernel<SVD, XG>: XG (npar > 320) keeps the work vector in global scratch and takes no LDS (slower; no limit)
     void (*post)(EngineDev, int, int, int, uint8_t *, int) = nullptr; size_t post_lds = 0;
     // KernelPlan::tile_factor: tile_factor_kernel<NC, NW> -- 4 NW neighbouring chains' packed matrices in LDS
     void (*factor)(EngineDev) = nullptr; unsigned factor_grid = 0, factor_block = 0; size_t factor_lds = 0;
-    // KernelPlan::svd_blocked: the sweep with all 32 lanes of a row group on pairs up to npar 200 (svd_sweep_stream32_kernel<RL>), 24
-    // pair-lanes (svd_sb) and a wave of loaders above (svd_sweep_stream_kernel<RL>); the log replayed on V (svd_applyv_stream32_kernel<RP>)
-    void (*sweep32)(double *, mcx_d2 *, uint8_t *, int *, int, int) = nullptr;
-    void (*sweep)(double *, mcx_d2 *, uint8_t *, int *, int, int, int) = nullptr; int svd_sb = 0;
-    size_t sweep_lds = 0;
-    void (*applyv)(double *, const mcx_d2 *, const uint8_t *, int, int) = nullptr; unsigned applyv_grid = 0; size_t applyv_lds = 0;
+    SvdPlan svd;                                       // KernelPlan::svd_blocked
 };
 // Which kernel forms the engine runs.  Decided ONCE, by plan_kernels at mcmcx_init (mcx_host_launch.hpp), from the configuration, the
 // problem's shape, the target kind, the switches and the CU count -- never from what was allocated; mcmcx_init allocates as it says and

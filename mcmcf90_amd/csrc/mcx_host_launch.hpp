@@ -290,7 +290,7 @@ static void launch_group_ram(mcmcx_engine *h, int it0, int it1)
 #include "../../tools/variants/variants.inc"
 #else
 #define MCX_VARIANT_STEP_ENTRIES
-#define MCX_VARIANT_SVD_SWEEP(h, lss) false
+#define MCX_VARIANT_SVD_SWEEP(stream, Gc, rot, state, anyrot, nlanes, d, lss) false
 #define MCX_VARIANT_COV(h, g8, n10, noff, it, mode) false
 #endif
 static const KernelEntry STEP_TABLE[] = {
@@ -474,14 +474,40 @@ static const KernelEntry PHASE_TABLE[] = {
     {"step", "pooled_phase_kernel", [](const mcmcx_engine *h) { return h->plan.pooled_phase == 1; }, nullptr, SH_R | SH_DR},
 };
 // the adaptation's SVD one workgroup per chain (mcx_svd.hpp) where its rings and row groups are instantiated
+static const int SVD_BLOCKED_MIN = 48, SVD_BLOCKED_MAX = 256;
 static bool svd_blocked(const mcmcx_engine *h, const mcx_switches &sw)
 {
     if (!h->usesvd || h->pooled || h->cfg.method == MCMCX_METHOD_RAM) return false;
     // test switch: the lane SVD (the engine's form below npar 48 and above 256)
     if (sw.svd_lane > 0) return false;
     // (its rings and row groups are instantiated up to npar 256)
-    return h->d >= 48 && h->d <= 256;
+    return h->d >= SVD_BLOCKED_MIN && h->d <= SVD_BLOCKED_MAX;
 }
+// the blocked SVD's forms (SvdPlan): from npar (SVD_BLOCKED_MIN .. SVD_BLOCKED_MAX) and the number of chains alone
+#define MCX_SVD_FORM(field, kernel) (a.field = kernel, #kernel)
+static SvdPlan plan_svd(int d, int nlanes)
+{
+    SvdPlan a;
+    if (d <= 200) {
+        const int RL = d <= 64 ? 8 : d <= 128 ? 16 : 25;
+        a.sweep_name = RL == 8 ? MCX_SVD_FORM(sweep32, svd_sweep_stream32_kernel<8>)
+            : RL == 16 ? MCX_SVD_FORM(sweep32, svd_sweep_stream32_kernel<16>) : MCX_SVD_FORM(sweep32, svd_sweep_stream32_kernel<25>);
+        a.sweep_lds = (size_t)33 * (8 * RL + 2) * sizeof(double);
+    } else {
+        const int RL = d <= 208 ? 26 : 32;
+        a.svd_sb = 24;                               // pair-lanes: whole waves of octets, one wave of loaders at least
+        a.sweep_name = RL == 26 ? MCX_SVD_FORM(sweep, svd_sweep_stream_kernel<26>) : MCX_SVD_FORM(sweep, svd_sweep_stream_kernel<32>);
+        a.sweep_lds = (size_t)(a.svd_sb + 2) * (8 * RL + 2) * sizeof(double);
+    }
+    const int RP = d <= 64 ? 4 : d <= 128 ? 8 : d <= 208 ? 13 : 16;
+    a.applyv_name = RP == 4 ? MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<4>)
+        : RP == 8 ? MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<8>)
+        : RP == 13 ? MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<13>) : MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<16>);
+    a.applyv_lds = (size_t)33 * (4 * RP + 6) * sizeof(double);
+    a.applyv_grid = (unsigned)(32 * ((nlanes + 7) / 8));                  // four one-wave workgroups per chain, a chain's on one XCD
+    return a;
+}
+#undef MCX_SVD_FORM
 // the adaptation tick's forms (AdaptPlan): from npar, the tile count and the plan's tile_factor / svd_blocked
 static void plan_adapt(const mcmcx_engine *h, KernelPlan &p)
 {
@@ -503,23 +529,7 @@ static void plan_adapt(const mcmcx_engine *h, KernelPlan &p)
         a.factor_lds = (size_t)ch * (h->P | 1) * sizeof(double) + (size_t)ch * sizeof(int);
         a.factor_grid = a.g8 * (unsigned)(64 / ch);
     }
-    if (p.svd_blocked) {
-        if (d <= 200) {
-            const int RL = d <= 64 ? 8 : d <= 128 ? 16 : 25;
-            a.sweep32 = RL == 8 ? svd_sweep_stream32_kernel<8> : RL == 16 ? svd_sweep_stream32_kernel<16> : svd_sweep_stream32_kernel<25>;
-            a.sweep_lds = (size_t)33 * (8 * RL + 2) * sizeof(double);
-        } else {
-            const int RL = d <= 208 ? 26 : 32;
-            a.svd_sb = 24;                               // pair-lanes: whole waves of octets, one wave of loaders at least
-            a.sweep = RL == 26 ? svd_sweep_stream_kernel<26> : svd_sweep_stream_kernel<32>;
-            a.sweep_lds = (size_t)(a.svd_sb + 2) * (8 * RL + 2) * sizeof(double);
-        }
-        const int RP = d <= 64 ? 4 : d <= 128 ? 8 : d <= 208 ? 13 : 16;
-        a.applyv = RP == 4 ? svd_applyv_stream32_kernel<4> : RP == 8 ? svd_applyv_stream32_kernel<8>
-            : RP == 13 ? svd_applyv_stream32_kernel<13> : svd_applyv_stream32_kernel<16>;
-        a.applyv_lds = (size_t)33 * (4 * RP + 6) * sizeof(double);
-        a.applyv_grid = (unsigned)(32 * ((h->nlanes + 7) / 8));            // four one-wave workgroups per chain, a chain's on one XCD
-    }
+    if (p.svd_blocked) a.svd = plan_svd(d, h->nlanes);
 }
 // ---- the plan: every kernel form the engine takes, decided once at mcmcx_init before anything is allocated.  Its inputs are the
 // configuration, the problem's shape, the target kind, the switches (read here, nowhere else) and the CU count; never a device pointer.

@@ -33,13 +33,15 @@ static int host_initial_R(int d, const std::vector<double> &cm, std::vector<doub
 }
 
 // The pinned dgesvd('A','N') of a symmetric PSD matrix (one-sided Jacobi), same operation sequence as the device's
-// symsvd_dev; used for the shared initial factor.  G, V column-major n*n.
+// symsvd_dev; used for the shared initial factor.  G, V column-major n*n.  Returns the routine's return value: the number of sweeps
+// that rotated (60 at the cap).
 static inline double h_tree8(const double *p) { return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7])); }
-static void host_symsvd(int n, std::vector<double> &G, std::vector<double> &V, std::vector<double> &sv)
+static int host_symsvd(int n, std::vector<double> &G, std::vector<double> &V, std::vector<double> &sv)
 {
     V.assign((size_t)n * n, 0.0); sv.assign(n, 0.0);
     for (int j = 0; j < n; ++j) V[(size_t)j * n + j] = 1.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
+    int sweep;
+    for (sweep = 0; sweep < 60; ++sweep) {
         bool rotated = false;
         for (int p = 0; p < n - 1; ++p)
             for (int q = p + 1; q < n; ++q) {
@@ -71,6 +73,7 @@ static void host_symsvd(int n, std::vector<double> &G, std::vector<double> &V, s
         for (int j = i + 1; j < n; ++j) if (sv[j] > sv[m]) m = j;
         if (m != i) { std::swap(sv[i], sv[m]); for (int k = 0; k < n; ++k) std::swap(V[(size_t)i * n + k], V[(size_t)m * n + k]); }
     }
+    return sweep;
 }
 
 // MCMC_calculate_R, SVD branches, for the shared initial covariance (MCMC_init.F90:109): returns 0 or an error code.

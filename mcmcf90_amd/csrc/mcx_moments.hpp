@@ -173,4 +173,18 @@ __global__ void debug_rng_kernel(uint32_t k0, uint32_t k1, int kind, int n, doub
     *nused = g.n;
 }
 
+// symsvd_dev on a caller's matrices (mcmcx_debug_symsvd, tests/test_gpu_svd.py): one wave per tile of 64, one lane per matrix, the arrays
+// interleaved as the engine stores them ([tile][element][64]); lanes past nmat and lanes with need == 0 pass act = false.  nsw[matrix]:
+// the number of sweeps the lane rotated in.
+__global__ __launch_bounds__(64) void debug_symsvd_kernel(double *Gt, double *Vt, double *sv_t, int *nsw, const uint8_t *need, int nmat,
+    int d)
+{
+    const int lane = threadIdx.x, tile = blockIdx.x, m = tile * 64 + lane;
+    const size_t DD = (size_t)d * d;
+    const bool act = m < nmat && need[m] != 0;
+    int n = 0;
+    symsvd_dev(Gt + (size_t)tile * DD * 64, Vt + (size_t)tile * DD * 64, sv_t + (size_t)tile * d * 64, lane, d, act, &n);
+    if (act) nsw[m] = n;
+}
+
 } // namespace mcx

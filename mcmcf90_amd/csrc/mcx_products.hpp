@@ -198,8 +198,10 @@ MCX_DEV double svd_tree8(const double (&p)[8]) { return ((p[0] + p[1]) + (p[2] +
 // The pinned dgesvd('A','N') of a symmetric PSD matrix: one-sided Jacobi, row-cyclic, operation for operation the
 // routine of oracle/mcx_svd.h (see there).  Gt: in the matrix (column-major d*d per chain), destroyed; Vt: out
 // the singular vectors; sv_t: out singular values, descending.  Lanes converge independently; a converged lane
-// keeps re-deriving "no rotation" from unchanged data, which is the same as having left the loop.
-MCX_DEV void symsvd_dev(double *Gt, double *Vt, double *sv_t, int lane, int d, bool act)
+// keeps re-deriving "no rotation" from unchanged data, which is the same as having left the loop.  nsweeps (the probe
+// debug_symsvd_kernel only; null in the engine, where the count compiles away): += 1 per sweep this lane rotated in -- the routine's
+// return value.
+MCX_DEV void symsvd_dev(double *Gt, double *Vt, double *sv_t, int lane, int d, bool act, int *nsweeps = nullptr)
 {
     for (int j = 0; j < d; ++j) for (int i = 0; i < d; ++i) if (act) GV(Vt, (size_t)j * d + i) = (i == j) ? 1.0 : 0.0;
     // One pass over k per pair: the rotation of (g_p, g_q) and (v_p, v_q) and, on the fly, the three dot products of
@@ -292,6 +294,7 @@ MCX_DEV void symsvd_dev(double *Gt, double *Vt, double *sv_t, int lane, int d, b
                 alpha = na; beta = nb; gamma = ng;
             }
         }
+        if (nsweeps && rotated) ++*nsweeps;
         if (!__any(rotated)) break;
     }
     if (act) {

@@ -973,6 +973,25 @@ def kernel_table():
     return out
 
 
+def debug_symsvd(form, A, need=None, device=0, fill=0.0, sweeps_fill=-1):
+    """Test probe (mcmcx_debug_symsvd): the pinned SVD of the symmetric matrices A[nmat, d, d] in the host's statement (form 0, no device),
+    the lane form (1) or the blocked kernels (2).  Returns (V[nmat, d, d] with the singular vectors as columns, s[nmat, d], sweeps[nmat],
+    forms); rows of matrices with need == 0 keep `fill` / `sweeps_fill`.  Raises RuntimeError on a refusal."""
+    L = _lib.load()
+    A = np.asarray(A, dtype=np.float64)
+    nmat, d = A.shape[0], A.shape[-1]
+    a = np.ascontiguousarray(np.swapaxes(A, 1, 2))                  # [m][column][row]: column-major d x d per matrix
+    V = np.full((nmat, d, d), fill, dtype=np.float64); s = np.full((nmat, d), fill, dtype=np.float64)
+    sweeps = np.full(nmat, sweeps_fill, dtype=np.int32)
+    nd = None if need is None else np.ascontiguousarray(np.asarray(need, dtype=np.uint8))
+    buf = C.create_string_buffer(256)
+    rc = L.mcmcx_debug_symsvd(device, form, d, nmat, _dp(a), None if nd is None else nd.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(V), _dp(s),
+                              sweeps.ctypes.data_as(C.POINTER(C.c_int32)), buf, 256)
+    if rc != 0:
+        raise RuntimeError("mcmcx_debug_symsvd: %d %s" % (rc, (L.mcmcx_last_error() or b"").decode()))
+    return np.swapaxes(V, 1, 2), s, sweeps, buf.value.decode()
+
+
 def engine_from_problem(cfg_kw, prob_kw, nchains=1, **extra):
     """Build an Engine from the same (cfg, problem) dictionaries the oracle / golden fixtures use."""
     pk = dict(prob_kw)

@@ -483,11 +483,14 @@ def test_history_ring_without_record_chain(oracle, kw, dr, kernels):
 @pytest.mark.parametrize("d,method,extra", [(48, "scam", {}), (49, "scam", {}), (70, "scam", {}), (64, "dram", dict(condmax=1e6)), (65, "dram", dict(condmax=1e6)),
                                             (100, "dram", dict(condmax=50.0, drscale=2.0)), (128, "scam", {}), (129, "scam", {}), (200, "dram", dict(condmax=1e6)),
                                             (200, "scam", {}), (209, "scam", {}), (225, "scam", {}),
-                                            pytest.param(255, "scam", {}, marks=pytest.mark.extended), pytest.param(256, "scam", {}, marks=pytest.mark.extended)])
+                                            pytest.param(255, "scam", {}, marks=pytest.mark.extended), pytest.param(256, "scam", {}, marks=pytest.mark.extended),
+                                            # (appended, so that the earlier cases keep their ids)
+                                            (201, "scam", {}), (208, "dram", dict(condmax=1e6))])
 def test_blocked_svd_equals_lane_svd_and_oracle(oracle, d, method, extra, monkeypatch):
     """npar 48..256 with an SVD factor: MCMC_adapt's factorisation runs one workgroup per chain (mcx_svd.hpp: the pinned routine's pairs in a
     reordered but equivalent sequence, every later column streamed past a block's pair-lanes -- svd_sweep_stream32_kernel up to npar 200,
-    svd_sweep_stream_kernel<26> up to 208 and <32> up to 256 (209, 225: both instances in the default suite), svd_applyv_stream32_kernel for V).
+    svd_sweep_stream_kernel<26> up to 208 and <32> up to 256 (201, 208: <26>; 209, 225: <32>; so both instances are in the default suite),
+    svd_applyv_stream32_kernel for V; every instance at both edges of its range on edge matrices: tests/test_gpu_svd.py).
     Bit for bit the one-lane-per-chain routine (MCMCX_SVD_LANE=1: the engine's own form below npar 48 and above 256; compared up to npar = 128)
     -- factor, singular values, states after several adaptations, a ragged tile -- and the oracle on two chains.  (The four superseded
     generations of these kernels and the shared-rotation negative were compared here up to round 5: tools/variants/README.md.)"""

@@ -20,15 +20,15 @@ static bool variant_pooled_ok(const mcmcx_engine *h) { return h->plan.pooled_mfm
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma2_kernel, dim3(h->ntiles), dim3(128), pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT}, \
     {"step", "step_kernel<false, true, false>", [](const mcmcx_engine *h) { return !h->pooled && kernel_method(h) != M_RAM && h->dodr && !phased(h) && variant_env("MCMCX_DR_GENERAL") == 1; }, \
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<false, true, false>), G1, lds_step(h), STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
-static bool variant_svd_sweep(mcmcx_engine *h, size_t lss)
+static bool variant_svd_sweep(hipStream_t stream, double *Gc, mcx_d2 *rot, uint8_t *state, int *anyrot, int nlanes, int d, size_t lss)
 {
     if (variant_env("MCMCX_SVD_SHARED_ROT") != 1) return false;
-    if (h->d <= 64) hipLaunchKernelGGL(svd_sweep_stream32s_kernel<8>, dim3(h->nlanes), dim3(256), lss, h->stream, h->d_Gc, (mcx_d2 *)h->E.Gw, h->d_state, h->d_anyrot, h->nlanes, h->d);
-    else if (h->d <= 128) hipLaunchKernelGGL(svd_sweep_stream32s_kernel<16>, dim3(h->nlanes), dim3(256), lss, h->stream, h->d_Gc, (mcx_d2 *)h->E.Gw, h->d_state, h->d_anyrot, h->nlanes, h->d);
-    else hipLaunchKernelGGL(svd_sweep_stream32s_kernel<25>, dim3(h->nlanes), dim3(256), lss, h->stream, h->d_Gc, (mcx_d2 *)h->E.Gw, h->d_state, h->d_anyrot, h->nlanes, h->d);
+    if (d <= 64) hipLaunchKernelGGL(svd_sweep_stream32s_kernel<8>, dim3(nlanes), dim3(256), lss, stream, Gc, rot, state, anyrot, nlanes, d);
+    else if (d <= 128) hipLaunchKernelGGL(svd_sweep_stream32s_kernel<16>, dim3(nlanes), dim3(256), lss, stream, Gc, rot, state, anyrot, nlanes, d);
+    else hipLaunchKernelGGL(svd_sweep_stream32s_kernel<25>, dim3(nlanes), dim3(256), lss, stream, Gc, rot, state, anyrot, nlanes, d);
     return true;
 }
-#define MCX_VARIANT_SVD_SWEEP(h, lss) variant_svd_sweep((h), (lss))
+#define MCX_VARIANT_SVD_SWEEP(stream, Gc, rot, state, anyrot, nlanes, d, lss) variant_svd_sweep((stream), (Gc), (rot), (state), (anyrot), (nlanes), (d), (lss))
 static bool variant_cov(mcmcx_engine *h, unsigned g8, int n10, int noff, int it, int mode)
 {
     if (variant_env("MCMCX_COV_FIFO") != 1) return false;
