@@ -97,6 +97,48 @@ const char *mcmcx_last_kernel(mcmcx_handle h);                /* the sampling ke
                                                                   (diagnostics) */
 
 int mcmcx_set_par0(mcmcx_handle h, const double *par0, int32_t npar);
+/* ---- Per-chain start points (no counterpart in the single-chain reference, which starts its one chain at par0).  By default every
+ * chain starts at par0; two calls, both before mcmcx_init and both off by default, give every chain a start of its own.  A run that uses
+ * neither is bit for bit the run without them.  Chain c is then the reference's single chain started at its start point: oldpar is the
+ * start, the first ss / sspri is evaluated there, chain row 1 is the start, chainmean is the start at init and at both restarts of the
+ * adaptation (the greedy restart of the burn-in, MCMC_adapt.F90:83-101, and the first AM tick); everything else is unchanged, the chain's
+ * stream (seed, chain_id0 + c) included.  mcmcx_set_par0 is still required: par0 stays the shift of the pooled moments and the pooled
+ * state's initial mean, and in pooled mode nothing but theta changes.  mcmcx_get_theta right after init returns the starts;
+ * mcmcx_set_samples with first = 1 keeps them as sample 0.  The later of the two calls wins.
+ *
+ * mcmcx_set_par0_all: par0_all is host memory, [nchains][npar] row-major like mcmcx_get_theta's rows, copied at the call.  A start
+ * outside the box of mcmcx_set_bounds is taken as it is, as par0 is.
+ *
+ * mcmcx_set_par0_spread: the starts are drawn on the device at mcmcx_init (start_spread_kernel).  The definition is the contract
+ * (tests/start_ref.py restates it with the oracle's generator):
+ *   Stream: chain c draws from its own Philox stream, key (seed, chain_id0 + c), starting at uniform number 2**63 with an empty polar
+ *     cache -- no run reaches that number, there is no new key and no new generator, the chain's sampling stream is not advanced, and the
+ *     starts do not depend on how the chains are sharded over engines.
+ *   Factor: U0 = dpotf2('U', cmat0) * 2.4 / sqrt(npar), the initial Cholesky proposal factor (what mcmcx_get_R shows after init on the
+ *     Cholesky path) -- with condmax > 0 and method = 'scam' too.  If that factorisation fails, mcmcx_init refuses.
+ *   One attempt: z_k = normal_bm(), k = 0 .. npar-1 in that order; x_j = the fma chain t = fma(U0(i,j), z_i, t) from +0.0, i ascending to j;
+ *     theta_k = par0_k + (scale * x_k): one multiplication, then one addition, no contraction.
+ *   Bounds: with mcmcx_set_bounds, an attempt the proposals' box test rejects is followed by another one from the next normals of the same
+ *     stream (the polar cache carries over), MCMCX_START_TRIES attempts at the most; after that the chain starts at par0, bit for bit.  A
+ *     user's checkbounds callback or module function is not consulted.
+ *   scale = 1 is one draw of the initial proposal distribution around par0; scale = sqrt(npar) / 2.4 is N(par0, cmat0).
+ *
+ * Cost: a device table of the starts, ceil(nchains / 64) x npar x 64 doubles, allocated only when one of the two calls was made (400 MB
+ * at 1 048 576 chains x npar 50).  mcmcx_set_par0_all also holds its copy of par0_all in host memory from the call until mcmcx_init has
+ * filled the device table (init stages a second, tile-interleaved host vector of that size for the upload); both are released there.
+ *
+ * mcmcx_start_info, after init: out3 = {mode: 0 shared par0, 1 given, 2 spread; chains that made more than one attempt; chains that fell
+ * back to par0}.  It is a getter and answers like the other getters, not with -56: -40 for a null handle or one that is not inited, -1
+ * for a null out3.
+ *
+ * The two setters refuse with -56 (the reason in mcmcx_last_error), nothing allocated or launched: a null handle or array; nchains or npar that differ
+ * from the handle's; a value of par0_all that is not finite; a scale that is not finite or not > 0 (0 is refused, not "off"); either call
+ * after mcmcx_init; mcmcx_set_target_external (mcmcx_init returns the -56 when the external target was chosen after the call); and at
+ * mcmcx_init, for spread, a cmat0 whose Cholesky factorisation failed. */
+#define MCMCX_START_TRIES 64
+int mcmcx_set_par0_all(mcmcx_handle h, const double *par0_all /* [nchains][npar] */, int32_t nchains, int32_t npar);
+int mcmcx_set_par0_spread(mcmcx_handle h, double scale);
+int mcmcx_start_info(mcmcx_handle h, int64_t *out3);
 int mcmcx_set_cmat0(mcmcx_handle h, const double *cmat0_colmajor, int32_t npar);
 int mcmcx_set_sigma2nobs(mcmcx_handle h, const double *sigma2, const int32_t *nobs, int32_t nycol);
 int mcmcx_set_target_gauss(mcmcx_handle h, const double *mu, const double *lam_rowmajor);
@@ -285,8 +327,9 @@ int mcmcx_get_samples_dev(mcmcx_handle h, int32_t s0, int32_t ns, int32_t c0, in
  *   positive, so ess is an UPPER bound (raise maxlag, or thin more).  maxlag = 0 gives K = 0 and no pairs: ess and mcse are NaN
  *   and truncated = 1 -- the R-hat-only mode.  Non-finite samples propagate.
  * Reading the numbers: with n_h short against the autocorrelation time split-R-hat sits above 1 even at stationarity (an AR(1)
- * with coefficient 0.5 and n_h = 32 gives 1.03, with 0.9 it gives 1.30): choose thin, not capacity, to fix it.  All chains start at
- * par0, so R-hat here measures stationarity within the window, not recovery from dispersed starts.
+ * with coefficient 0.5 and n_h = 32 gives 1.03, with 0.9 it gives 1.30): choose thin, not capacity, to fix it.  Unless the chains
+ * were given start points of their own (mcmcx_set_par0_all, mcmcx_set_par0_spread) they all start at par0, and R-hat then measures
+ * stationarity within the window, not recovery from dispersed starts.
  * mcmcx_samples_stats copies the vector to host memory and synchronises; mcmcx_samples_stats_dev writes it into the caller's DEVICE
  * buffer, asynchronous on the engine's stream.  shift, if given, is host memory in both forms; it is staged during the call, so it need
  * only stay valid until the call returns.  Refused with -49 (the reason in
@@ -323,7 +366,8 @@ int mcmcx_samples_diag(const double *stats, int32_t nfields, int32_t maxlag, dou
  *   Non-finite values propagate as the arithmetic says (kind 1 maps every value, NaNs included, to 1.0 or +0.0).  An indicator that is
  *   constant over the window -- a_f below or above every value -- has G_0 = 0, so W = 0 and its R-hat and ESS are NaN (0 / 0), not 1.
  * Reading the numbers: tail ESS is the smaller ess of kind 1 at the 5 % and the 95 % quantile; the MCSE of P(x <= q) is
- * sqrt(p (1 - p) / ess).  Folded split-R-hat is rhat of kind 2 at the median: all chains start at par0, so the plain R-hat measures
+ * sqrt(p (1 - p) / ess).  Folded split-R-hat is rhat of kind 2 at the median: when all chains start at par0 (no mcmcx_set_par0_all /
+ * mcmcx_set_par0_spread) the plain R-hat measures
  * drift, and chains that agree in location but differ in scale show only here.  The MCSE of the sd is mcse / (2 sd) of kind 3 at the
  * mean (the delta method on the variance).  For an indicator a shift of zeros is exact (every y is 0 or 1).
  * a and shift are host memory in both forms and are staged during the call.  mcmcx_samples_stats_of copies the vector to host memory

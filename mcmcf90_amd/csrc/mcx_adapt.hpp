@@ -359,6 +359,7 @@ __global__ __launch_bounds__(64) void adapt_pre_kernel(EngineDev E, int it, int 
     double *Rt = E.R + (size_t)tile * P * 64;
     double *Ct = E.cmat + (size_t)tile * P * 64;
     double *mean_t = E.mean + (size_t)tile * d * 64;
+    const double *start_t = E.start ? E.start + (size_t)tile * d * 64 : nullptr;    // the chains' own start points, or all at par0
     uint64_t *rows = E.rowlist + (size_t)tile * (E.wcap + 1) * 64;
     uint32_t stayed = TIDX(E.ictr, tile, NICTR, I_STAYED, lane);
     uint32_t curcount = TIDX(E.ictr, tile, NICTR, I_CURCOUNT, lane);
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(64) void adapt_pre_kernel(EngineDev E, int it, int 
             flags |= ADF_GREEDY;
             wsum = E.initcmatn;
             for (int e = 0; e < P; ++e) GV(Ct, e) = E.cmat0p[e];
-            for (int k = 0; k < d; ++k) GV(mean_t, k) = E.par0[k];
+            for (int k = 0; k < d; ++k) GV(mean_t, k) = E.start ? GV(start_t, k) : E.par0[k];
             if (wsum > 0.0) flags |= ADF_STEADY;
             else {
                 for (int t = 1; t <= it; ++t) {                       // row list of the one-off batch branch
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(64) void adapt_pre_kernel(EngineDev E, int it, int 
         if (mode & AD_FIRST) {
             wsum = E.initcmatn;
             for (int e = 0; e < P; ++e) GV(Ct, e) = E.cmat0p[e];
-            for (int k = 0; k < d; ++k) GV(mean_t, k) = E.par0[k];
+            for (int k = 0; k < d; ++k) GV(mean_t, k) = E.start ? GV(start_t, k) : E.par0[k];
         }
         if (E.adapthist > 1) {
             // AP (:116-136): rows back from chainind until the repeat counts cover adapthist iterations; the oldest

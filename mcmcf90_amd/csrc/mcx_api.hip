@@ -170,6 +170,45 @@ int mcmcx_set_par0(mcmcx_handle h, const double *p, int32_t n)
     h->par0.assign(p, p + n);
     return 0;
 }
+// ---- per-chain start points (include/mcmcx.h, "Per-chain start points"): given by the caller, or drawn on the device at mcmcx_init
+// (start_spread_kernel).  The later call wins; every refusal is -56 and changes nothing.
+static_assert(MCMCX_START_TRIES == START_TRIES, "include/mcmcx.h and mcx_start.hpp disagree about the attempts of a drawn start");
+static int start_refused(mcmcx_handle h, const char *who)
+{
+    if (!h) return fail(-56, std::string(who) + ": null handle");
+    if (h->inited) return fail(-56, std::string(who) + " after mcmcx_init (the start points are set there)");
+    if (h->external) return fail(-56, std::string(who) + ": not with mcmcx_set_target_external (the caller holds the chains' states)");
+    return 0;
+}
+int mcmcx_set_par0_all(mcmcx_handle h, const double *par0_all, int32_t nchains, int32_t npar)
+{
+    int rc = start_refused(h, "mcmcx_set_par0_all"); if (rc) return rc;
+    if (!par0_all) return fail(-56, "mcmcx_set_par0_all: null array");
+    if (nchains != h->cfg.nchains || npar != h->d) return fail(-56, "mcmcx_set_par0_all: the array is [" + std::to_string(nchains) + "]["
+        + std::to_string(npar) + "] but the handle has nchains = " + std::to_string(h->cfg.nchains) + ", npar = " + std::to_string(h->d));
+    const size_t n = (size_t)nchains * npar;
+    for (size_t e = 0; e < n; ++e) if (!std::isfinite(par0_all[e])) return fail(-56, "mcmcx_set_par0_all: a value that is not finite "
+        "(chain " + std::to_string(e / npar) + ", parameter " + std::to_string(e % npar) + ")");
+    h->start_all.assign(par0_all, par0_all + n);
+    h->start_mode = 1;
+    return 0;
+}
+int mcmcx_set_par0_spread(mcmcx_handle h, double scale)
+{
+    int rc = start_refused(h, "mcmcx_set_par0_spread"); if (rc) return rc;
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(-56, "mcmcx_set_par0_spread: scale must be finite and > 0");
+    h->start_scale = scale;
+    h->start_mode = 2;
+    std::vector<double>().swap(h->start_all);
+    return 0;
+}
+int mcmcx_start_info(mcmcx_handle h, int64_t *out3)
+{
+    if (!h || !h->inited) return fail(-40, "we have not inited");
+    if (!out3) return fail(-1, "mcmcx_start_info: null argument");
+    out3[0] = h->start_mode; out3[1] = h->start_redrew; out3[2] = h->start_fell;
+    return 0;
+}
 int mcmcx_set_cmat0(mcmcx_handle h, const double *c, int32_t n)
 {
     if (!h || !c) return fail(-1, "null argument");
@@ -339,6 +378,8 @@ static int init_check(mcmcx_engine *h)
     if (h->tkind < 0) return fail(-31, "no target: the device engine needs mcmcx_set_target_*");
     if (h->external && h->samp.thin > 0) return fail(-47, "mcmcx_set_samples: not with mcmcx_set_target_external (the caller drives the "
         "iterations)");
+    if (h->external && h->start_mode) return fail(-56, "per-chain start points: not with mcmcx_set_target_external (the caller holds the "
+        "chains' states)");
     return 0;
 }
 static int initial_factor(mcmcx_engine *h, InitialFactor &f)
@@ -351,6 +392,9 @@ static int initial_factor(mcmcx_engine *h, InitialFactor &f)
     if (h->ny > 1 && h->pooled && h->plan.fused_cols && c.method == MCMCX_METHOD_SCAM)
         return fail(-36, "nycol > 1 in pooled mode: not with method = 'scam' on the device-resident response-column target");
     int info = host_initial_R(d, h->cmat0, f.Rp, f.Cp);
+    // the drawn starts are par0 + scale U0'z with U0 this Cholesky factor, whatever factor the proposals use (condmax > 0, SCAM)
+    if (h->start_mode == 2 && info != 0) return fail(-56, "mcmcx_set_par0_spread: could not factor the initial covariance (dpotf2 stopped "
+        "at column " + std::to_string(info) + "): the starts are drawn with its Cholesky factor");
     if (h->usesvd) {                                                                  // Cp (packed cmat0) is still needed
         if (info != 0) { f.Rp.assign(P, 0.0); info = 0; }
         info = host_initial_svd(d, h->cmat0, c.condmax, c.method == MCMCX_METHOD_SCAM, f.Rfull, f.qstd);
@@ -424,6 +468,7 @@ static int init_chains(mcmcx_engine *h, const InitialFactor &f)
     if ((rc = dev_alloc(h, &E.rngn, L))) return rc;
     if (!h->pooled && (rc = dev_alloc(h, &E.R, L * P, false))) return rc;          // pooled: one shared factor instead
     if ((rc = dev_alloc(h, &E.basetheta, L * d))) return rc;
+    if (h->start_mode && (rc = dev_alloc(h, &E.start, L * d, false))) return rc;       // the chains' own start points (init_starts)
     if (h->usesvd && !h->pooled) {                      // (pooled: pooled_alloc)
         if ((rc = dev_alloc(h, &E.Rf, L * DD, false))) return rc;
         if (c.method != MCMCX_METHOD_RAM) {                 // work space of the adaptation's SVD; RAM never refactors
@@ -501,7 +546,48 @@ static int init_run_buffers(mcmcx_engine *h)
     if ((rc = dev_alloc(h, &h->d_gather, (size_t)(h->comm ? h->comm->nranks : 1) * (3 + d + P)))) return rc;   // ... + the stop flag
     return dev_alloc(h, &h->d_pooled, (size_t)(3 + d + P));
 }
-// fill theta = par0, R = R(cmat0), chaincmat = cmat0, chainmean = par0, scalars; the first evaluation
+// E.start, when the chains have start points of their own: the caller's rows (padding lanes of the last tile: par0), or drawn by
+// start_spread_kernel with the shared packed factor U0 = f.Rp; dst (theta, chainmean) is then a copy of it instead of par0's broadcast
+static int init_starts(mcmcx_engine *h, const InitialFactor &f)
+{
+    EngineDev &E = h->E;
+    const int d = h->d, T = h->ntiles, N = h->cfg.nchains;
+    h->start_redrew = h->start_fell = 0;
+    if (h->start_mode == 1) {
+        std::vector<double> st((size_t)T * 64 * d);
+        for (int c = 0; c < T * 64; ++c)
+            for (int k = 0; k < d; ++k)
+                st[((size_t)(c / 64) * d + k) * 64 + (c % 64)] = c < N ? h->start_all[(size_t)c * d + k] : h->par0[k];
+        HIPCHK(hipMemcpyAsync(E.start, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        std::vector<double>().swap(h->start_all);       // the device table holds them now: the host copy of the call is released
+        return 0;
+    }
+    DevBufs tmp;
+    double *U0 = nullptr; uint32_t *tries = nullptr;
+    HIPCHK(tmp.alloc(&U0, f.Rp.size() * sizeof(double)));
+    HIPCHK(tmp.alloc(&tries, (size_t)T * 64 * sizeof(uint32_t)));
+    HIPCHK(hipMemcpyAsync(U0, f.Rp.data(), f.Rp.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(start_spread_kernel, dim3(T), dim3(64), 0, h->stream, E, (const double *)U0, h->start_scale, N, tries);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(E.zs, 0, (size_t)T * 64 * 2 * d * sizeof(double), h->stream));     // the attempts' normals: scratch as allocated
+    std::vector<uint32_t> tr((size_t)T * 64);
+    HIPCHK(hipMemcpyAsync(tr.data(), tries, tr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int c = 0; c < N; ++c) {
+        if ((tr[c] & ~START_FELL_BACK) > 1u) h->start_redrew += 1;
+        if (tr[c] & START_FELL_BACK) h->start_fell += 1;
+    }
+    return 0;
+}
+static int fill_start(mcmcx_engine *h, double *dst)         // dst = every chain's start: par0, or its row of E.start
+{
+    if (!h->E.start) return dev_bcast(h, dst, h->par0);
+    HIPCHK(hipMemcpyAsync(dst, h->E.start, (size_t)h->ntiles * 64 * h->d * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+// fill theta = the start (par0), R = R(cmat0), chaincmat = cmat0, chainmean = the start, scalars; the first evaluation
 static int init_fill(mcmcx_engine *h, const InitialFactor &f)
 {
     const mcmcx_config &c = h->cfg;
@@ -522,10 +608,11 @@ static int init_fill(mcmcx_engine *h, const InitialFactor &f)
     HIPCHK(hipMemcpyAsync(E.ictr, ic.data(), ic.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     int rc;
-    if ((rc = dev_bcast(h, E.theta, h->par0))) return rc;
+    if (h->start_mode && (rc = init_starts(h, f))) return rc;
+    if ((rc = fill_start(h, E.theta))) return rc;
     if (!h->pooled && (rc = dev_bcast(h, E.R, f.Rp))) return rc;
     if (h->dodr && !h->pooled && ((rc = dev_bcast(h, E.R2, f.R2p)) || (rc = dev_bcast(h, E.iC, f.iCp)))) return rc;
-    if (h->plan.am && ((rc = dev_bcast(h, E.cmat, f.Cp)) || (rc = dev_bcast(h, E.mean, h->par0)))) return rc;
+    if (h->plan.am && ((rc = dev_bcast(h, E.cmat, f.Cp)) || (rc = fill_start(h, E.mean)))) return rc;
     // first point: sspri1, ss1 from the callbacks (MCMC_run.F90:35-36) -- with MCMC_run1 every evaluation is the caller's, this one too
     if (!h->external && phased(h) && (rc = host_eval(h, E.theta, h->d, false))) return rc;
     launch_init(h);
@@ -875,9 +962,13 @@ int mcmcx_get_chaincov(mcmcx_handle h, int32_t chain, double *cmat, double *mean
     std::vector<double> s;
     if ((rc = fetch_chain_vec(h, h->E.scal, NSCAL, chain, s))) return rc;
     if (wsum) *wsum = s[S_WSUM];
-    if (!h->E.cmat) {                                   // no AM state on the device: chaincmat = cmat0, chainmean = par0
+    if (!h->E.cmat) {                                   // no AM state on the device: chaincmat = cmat0, chainmean = the chain's start
         if (cmat) memcpy(cmat, h->cmat0.data(), sizeof(double) * (size_t)h->d * h->d);
-        if (mean) memcpy(mean, h->par0.data(), sizeof(double) * (size_t)h->d);
+        if (mean && h->E.start) {
+            std::vector<double> m;
+            if ((rc = fetch_chain_vec(h, h->E.start, h->d, chain, m))) return rc;
+            memcpy(mean, m.data(), sizeof(double) * (size_t)h->d);
+        } else if (mean) memcpy(mean, h->par0.data(), sizeof(double) * (size_t)h->d);
         return 0;
     }
     std::vector<double> p, m;

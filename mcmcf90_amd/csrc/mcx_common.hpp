@@ -49,6 +49,9 @@ struct EngineDev {
     double *xscr;
     double *cmat, *mean, *basetheta;
     const double *cmat0p, *par0;    // packed upper cmat0 [P], par0 [d] (shared by all chains)
+    // every chain's own start point (mcmcx_set_par0_all / mcmcx_set_par0_spread), tile-interleaved [tile][d][64]; nullptr: all chains
+    // start at par0.  What a restart of the adaptation sets chainmean to (adapt_pre_kernel)
+    double *start;
     uint32_t *ictr;
     uint64_t *rngn;
     uint32_t k0, chain_id0;

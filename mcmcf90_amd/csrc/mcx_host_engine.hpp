@@ -135,6 +135,9 @@ struct mcmcx_engine {
     std::string launch_err;             // set by a launcher that found no kernel for the configuration: the run fails with it
     // host copies of the problem
     std::vector<double> par0, cmat0;                 // cmat0 col-major d*d
+    // per-chain start points: 0 all chains at par0, 1 given (start_all, [nchains][npar] row-major), 2 drawn on the device at
+    // mcmcx_init (start_scale); after init, the chains that made more than one attempt and those that fell back to par0
+    int start_mode = 0; std::vector<double> start_all; double start_scale = 0.0; long long start_redrew = 0, start_fell = 0;
     double sigma2 = 1.0; int nobs = 1; bool sigma2ok = false;
     int ny = 1; std::vector<double> sigma2v; std::vector<int> nobsv;      // nycol columns (host callbacks only when > 1)
     int tkind = -1, tncols = 1; std::vector<double> tmu, tlam, tx, ty, tlo, thi, tpmu, tpsig; double tb = 0.1;

@@ -18,6 +18,7 @@
 //   mcx_phase.hpp     host_phase_kernel<0..7>, dev_eval_kernel, step_kernel_cols (nycol >= 1), run1_kernel
 //   mcx_pooled_phase.hpp  pooled_phase_kernel / pooled_phase_mfma_kernel (pooled mode with a user module or host callbacks)
 //   mcx_adapt.hpp     init_kernel, adapt_pre / adapt_cov_diag / adapt_cov_off / adapt_covb_* / adapt_post kernels
+//   mcx_start.hpp     start_spread_kernel (per-chain start points drawn on the device, mcmcx_set_par0_spread)
 //   mcx_svd.hpp       svd_sweep_stream(32)_kernel, svd_applyv_stream32_kernel, tile <-> chain layout conversion
 //   mcx_moments.hpp   moments_kernel, moments_tree_kernel, debug kernels
 //   mcx_samples.hpp   samples_keep_kernel, samples_read_rows_kernel / samples_read_chains_kernel (the thinned sample store)
@@ -38,6 +39,7 @@
 #include "mcx_phase.hpp"
 #include "mcx_pooled_phase.hpp"
 #include "mcx_adapt.hpp"
+#include "mcx_start.hpp"
 #include "mcx_svd.hpp"
 #include "mcx_moments.hpp"
 #include "mcx_samples.hpp"

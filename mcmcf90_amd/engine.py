@@ -311,6 +311,24 @@ class Engine:
         a = _f64(par0)
         self._chk(self.L.mcmcx_set_par0(self.h, _dp(a), a.size))
 
+    def setpar0_all(self, par0_all):
+        """Every chain its own start point: par0_all[nchains, npar] (mcmcx_set_par0_all).  Before init; setpar0 is still required."""
+        a = np.ascontiguousarray(np.asarray(par0_all, dtype=np.float64))
+        if a.ndim != 2:
+            raise McmcError("setpar0_all: par0_all must be [nchains][npar]")
+        self._chk(self.L.mcmcx_set_par0_all(self.h, _dp(a), a.shape[0], a.shape[1]))
+
+    def setpar0_spread(self, scale=1.0):
+        """Start points drawn on the device at init, par0 + scale U0'z per chain (mcmcx_set_par0_spread; tests/start_ref.py restates the
+        draw).  scale = 1: one draw of the initial proposal; sqrt(npar) / 2.4: N(par0, cmat0)."""
+        self._chk(self.L.mcmcx_set_par0_spread(self.h, float(scale)))
+
+    def start_info(self):
+        """After init: how the chains were started (mcmcx_start_info)."""
+        a = np.zeros(3, dtype=np.int64)
+        self._chk(self.L.mcmcx_start_info(self.h, a.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(mode=("shared", "given", "spread")[int(a[0])], redrew=int(a[1]), fell_back=int(a[2]))
+
     def setcmat0(self, cmat0):
         a = np.asfortranarray(np.asarray(cmat0, dtype=np.float64))
         self._chk(self.L.mcmcx_set_cmat0(self.h, a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0]))

@@ -72,8 +72,15 @@ module mcmcmod
   !!                  modulekernel (the MCMCX_DEFINE_TARGET name), moduledatafile (numbers handed to the functions)
   integer, save :: hostbatch = 0, hostthreads = 1
   character(len=256), save :: modulefile = '', modulekernel = 'user_target', moduledatafile = ''
+  !! per-chain start points (include/mcmcx.h, "Per-chain start points"; every chain starts at par0 by default):
+  !!   startfile:  a file in mcmclaststates.dat's format, nchains rows of npar numbers, row c = the start of chain c (with ngpus > 1
+  !!               every engine gets its block of rows); startfile = 'mcmclaststates.dat' continues every chain where the last run stopped
+  !!   startscale: > 0: the starts are drawn on the device, par0 + startscale * U0'z per chain (mcmcx_set_par0_spread); 0 = off
+  !!   (MCMC_setpar0_all(par0all) gives the rows from the program; a startfile wins over it, both win over startscale)
+  real(kind=dbl), save :: startscale = 0.0_dbl
+  character(len=256), save :: startfile = ''
   namelist /mcmcx/ devtarget, nchains, seed, pooled, banana_b, mufile, lamfile, datafile, lowerfile, upperfile, ngpus, &
-       hostbatch, hostthreads, modulefile, modulekernel, moduledatafile, usecomm, scamfast
+       hostbatch, hostthreads, modulefile, modulekernel, moduledatafile, usecomm, scamfast, startscale, startfile
 
   !! public state, mcmc.F90:28-52
   integer, save :: npar = 0, nycol = 1, simuind = 0, chainind = 0, MCMC_running = 0
@@ -86,6 +93,7 @@ module mcmcmod
 
   !! set by the MCMC_set* calls
   real(kind=dbl), allocatable, save, private :: par0(:), cmat0(:,:)
+  real(kind=dbl), allocatable, save, private :: par0all(:,:)         ! (nchains, npar): every chain's own start, or not allocated
   real(kind=dbl), allocatable, save, private :: tmu(:), tlam(:,:), tx(:), ty(:), tlo(:), thi(:), pmu(:), psig(:), moddata(:)
   logical, save, private :: par0ok = .false., cmat0ok = .false., sigma2ok = .false., nparok = .false.
   logical, save, private :: has_lo = .false., has_hi = .false., interrupted = .false.
@@ -137,6 +145,19 @@ module mcmcmod
        type(c_ptr), value :: h
        real(c_double), intent(in) :: p(*)
        integer(c_int32_t), value :: n
+       integer(c_int) :: rc
+     end function
+     function mcmcx_set_par0_all(h, p, nch, n) bind(C, name='mcmcx_set_par0_all') result(rc)
+       import :: c_ptr, c_int, c_double, c_int32_t
+       type(c_ptr), value :: h
+       real(c_double), intent(in) :: p(*)
+       integer(c_int32_t), value :: nch, n
+       integer(c_int) :: rc
+     end function
+     function mcmcx_set_par0_spread(h, scale) bind(C, name='mcmcx_set_par0_spread') result(rc)
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: h
+       real(c_double), value :: scale
        integer(c_int) :: rc
      end function
      function mcmcx_set_cmat0(h, c, n) bind(C, name='mcmcx_set_cmat0') result(rc)
@@ -450,6 +471,13 @@ contains
     if (stat /= 0) call doerror('Error reading file '//trim(file))
     call MCMC_setpar0_vec(v)
   end subroutine MCMC_setpar0_file
+  !! every chain its own start point: par0all(nchains, npar), the shape of laststates (engine extension; MCMC_setpar0 is still needed)
+  subroutine MCMC_setpar0_all(par0all_in)
+    real(kind=dbl), intent(in) :: par0all_in(:,:)
+    if (nparok .and. npar /= size(par0all_in, 2)) call doerror('par0all and npar dont match')
+    if (allocated(par0all)) deallocate(par0all)
+    allocate(par0all(size(par0all_in, 1), size(par0all_in, 2))); par0all = par0all_in
+  end subroutine MCMC_setpar0_all
   subroutine MCMC_setcmat0_mat(cmat)
     real(kind=dbl), intent(in) :: cmat(:,:)
     if (nparok .and. npar /= size(cmat,1)) call doerror('cmat0 and npar dont match')
@@ -743,7 +771,8 @@ contains
     real(kind=dbl) :: lamrow(npar*npar)
     type(c_ptr) :: plo, phi
     real(kind=dbl), allocatable :: th(:), pm(:)
-    integer :: i, j, g, upto, nxt, nloc, stbits
+    integer :: i, j, g, upto, nxt, nloc, stbits, snr, snc, sstat
+    real(kind=dbl), allocatable :: sv(:), sblk(:)
     integer(c_int) :: rc
     interface
        subroutine dump_init()
@@ -784,6 +813,20 @@ contains
              lamrow((i-1)*npar + j) = tlam(i,j)
           end do
        end do
+    end if
+    if (len_trim(startfile) > 0) then                   ! nchains rows of npar numbers, mcmclaststates.dat's format
+       call loadnumbers(trim(startfile), sv, snr, snc, sstat)
+       if (sstat /= 0) call doerror('Error reading file '//trim(startfile))
+       if (snr /= nchains .or. snc /= npar) call doerror('&mcmcx startfile: the file must hold nchains rows of npar numbers')
+       if (allocated(par0all)) deallocate(par0all)
+       allocate(par0all(nchains, npar))
+       par0all = transpose(reshape(sv(1:nchains*npar), (/npar, nchains/)))
+    end if
+    if (.not. (startscale >= 0.0_dbl) .or. startscale > huge(startscale)) &        ! negative, NaN or infinite
+         call doerror('&mcmcx startscale must be finite and >= 0 (0 = off: every chain starts at par0)')
+    if (allocated(par0all)) then
+       if (size(par0all, 1) /= nchains .or. size(par0all, 2) /= npar) call doerror('MCMC_setpar0_all: par0all must be (nchains, npar)')
+       allocate(sblk(nloc*npar))
     end if
     plo = c_null_ptr; phi = c_null_ptr
     if (has_lo) then
@@ -830,6 +873,12 @@ contains
        end select
        if (has_lo .or. has_hi) call chk(mcmcx_set_bounds(handle, plo, phi))
        if (allocated(pmu)) call chk(mcmcx_set_priors(handle, pmu, psig))
+       if (allocated(par0all)) then                      ! this engine's block of rows, row-major like mcmcx_get_theta's
+          sblk = reshape(transpose(par0all((g-1)*nloc+1 : g*nloc, :)), (/nloc*npar/))
+          call chk(mcmcx_set_par0_all(handle, sblk, int(nloc, c_int32_t), int(npar, c_int32_t)))
+       else if (startscale > 0.0_dbl) then
+          call chk(mcmcx_set_par0_spread(handle, startscale))
+       end if
        call chk(mcmcx_init(handle))
     end do
     handle = handles(1)
