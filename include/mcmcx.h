@@ -758,6 +758,28 @@ int mcmcx_debug_samples_stats_step(int32_t device, int32_t nchains, int32_t nfie
  * is looked for: a null A, V_out or s_out, d < 1, nmat < 1, an unknown form, form 2 outside npar 48 .. 256, a len too small. */
 int mcmcx_debug_symsvd(int32_t device, int32_t form, int32_t d, int32_t nmat, const double *A, const uint8_t *need, double *V_out,
                        double *s_out, int32_t *sweeps_out, char *forms, int32_t len);
+/* The adaptation tick's own factorisation -- MCMC_calculate_R: dpotf2, the 2.4 / sqrt(npar) scaling, with delayed rejection dpotri and
+ * R2 = R / drscale; with condmax > 0 the SVD branch -- on a caller's covariances, in the kernel instances the engine's plan chose (no
+ * counterpart in the reference; tests only).  h: an initialised per-chain adaptive engine (not pooled, not method = 'ram', doadapt or
+ * doburnin set).  cmat: [nchains][npar * npar] column-major symmetric, host, its upper triangle packed into the chains' covariance
+ * (chains with need == 0 keep theirs); need: [nchains] host, 0 = this chain does not recompute, or NULL = all.  The entry sets the
+ * chains' tick flags to "recompute the factor" where need and to nothing elsewhere (and restores them), presets the chains' LAPACK
+ * info to MCMCX_DEBUG_INFO_SENTINEL, launches what the tick launches for the factorisation -- the same function, with mode 0, in which
+ * the covariance bookkeeping rewrites what it read -- and synchronises.  info_out[nchains] takes the chains' info as the kernels left
+ * it: 0, dpotf2's failing pivot (1-based; the SVD branch: npar when the largest singular value is 0), the sentinel where need == 0.
+ * forms: NULL, or a buffer of len bytes for the names of what ran: "adapt_post_kernel<false,false>", or
+ * "adapt_post_kernel<false,false>:3+tile_factor_kernel<2,4>" (the number is the phase), or for the blocked SVD
+ * "adapt_post_kernel<true,false>:1+<sweep>+<replay>+adapt_post_kernel<true,false>:2".  R, R2, iC, the status bits and the (floored)
+ * covariance are read with mcmcx_get_R, mcmcx_get_dr, mcmcx_get_counters and mcmcx_get_chaincov.  Refusals are -57, decided before
+ * anything is written or launched: a null h, cmat or info_out, an engine that is not initialised, pooled, method = 'ram' or without
+ * adaptation, a len too small. */
+#define MCMCX_DEBUG_INFO_SENTINEL (-77)
+int mcmcx_debug_calculate_R(mcmcx_handle h, const double *cmat, const uint8_t *need, int32_t *info_out, char *forms, int32_t len);
+/* The host's statement of the same (the shared initial factor's host_initial_R and host_potri; no device, no handle): A [d * d]
+ * column-major symmetric; R_out [d * d] takes the scaled factor's upper triangle (zeros below) and info_out[0] dpotf2's info; when that
+ * is 0, iC_out [d * d] (may be NULL) takes dpotri's result on R and info_out[1] its info (a zero on the diagonal: iC_out untouched).
+ * Refused with -57, nothing written: a null A, R_out or info_out, d outside 1 .. 4096. */
+int mcmcx_debug_host_calculate_R(int32_t d, const double *A, double *R_out, double *iC_out, int32_t *info_out);
 /* the host build of the key map the order statistics sort by (no counterpart in the reference): the key of x's bits, or with
  * inverse != 0 the bits whose key x's bits are.  Needs no device. */
 int64_t mcmcx_debug_quant_key(double x, int32_t inverse);

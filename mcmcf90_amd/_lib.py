@@ -161,6 +161,9 @@ SYMBOLS["mcmcx_samples_rank_scores"] = (C.c_int, [_LP, C.c_int32, C.c_int32, _DP
 # the adaptation's SVD on a caller's matrices: the host's, the lane form, the blocked kernels (tests)
 SYMBOLS["mcmcx_debug_symsvd"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, C.POINTER(C.c_uint8), _DP, _DP, _IP, C.c_char_p,
                                             C.c_int32])
+# the tick's own factorisation on a caller's covariances, in the engine's instances; the host's statement of it (tests)
+SYMBOLS["mcmcx_debug_calculate_R"] = (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_uint8), _IP, C.c_char_p, C.c_int32])
+SYMBOLS["mcmcx_debug_host_calculate_R"] = (C.c_int, [C.c_int32, _DP, _DP, _DP, _IP])
 # per-chain start points: given by the caller, or drawn on the device at init
 SYMBOLS["mcmcx_set_par0_all"] = (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32])
 SYMBOLS["mcmcx_set_par0_spread"] = (C.c_int, [C.c_void_p, C.c_double])

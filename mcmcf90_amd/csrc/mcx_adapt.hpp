@@ -837,8 +837,14 @@ __global__ __launch_bounds__(64, SVD ? 1 : MCX_POST_WAVES) void adapt_post_kerne
                         map_vec(Rft, Vt, lane, d * d, [&](double v) { return v * 2.4 / sqd; });
                         if (E.dodr) {                                 // iC = dpotri('u', R): on R's upper triangle; R2 = R/drscale
                             double *iCt = E.iC + (size_t)tile * P * 64, *R2ft = E.R2f + (size_t)tile * d * d * 64;
-                            for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i) GV(iCt, pidx(i, j, d)) = GV(Rft, (size_t)j * d + i);
-                            int info2 = potri_packed(iCt, lane, d, true, X);
+                            // dpotri's singularity test before the copy: a zero on the factor's diagonal (the reference stops) leaves
+                            // the inverse the chain had -- R and R2 are the new factor's
+                            int info2 = 0;
+                            for (int j = 0; j < d; ++j) if (info2 == 0 && GV(Rft, (size_t)j * d + j) == 0.0) info2 = j + 1;
+                            const bool inv = info2 == 0;
+                            if (inv) for (int j = 0; j < d; ++j) for (int i = 0; i <= j; ++i)
+                                GV(iCt, pidx(i, j, d)) = GV(Rft, (size_t)j * d + i);
+                            potri_packed(iCt, lane, d, inv, X);
                             if (info2 != 0) TIDX(E.ictr, tile, NICTR, I_STATUS, lane) |= ST_POTRI_FAIL;
                             map_vec(R2ft, Rft, lane, d * d, [&](double v) { return v / E.drscale; });
                         }
@@ -856,6 +862,7 @@ __global__ __launch_bounds__(64, SVD ? 1 : MCX_POST_WAVES) void adapt_post_kerne
         if (E.dodr) {                                       // iC = dpotri(R), R2 = R/drscale (:216-225)
             const bool ok = docalc && info == 0;
             double *R2t = E.R2 + (size_t)tile * P * 64, *iCt = E.iC + (size_t)tile * P * 64;
+            // (info2 != 0 cannot follow a successful dpotf2: every pivot was > 0 and a positive double's root, scaled, is not zero)
             if (ok) copy_vec(iCt, Rt, nullptr, lane, P);
             int info2 = potri_packed(iCt, lane, d, ok, X);
             if (ok && info2 != 0) TIDX(E.ictr, tile, NICTR, I_STATUS, lane) |= ST_POTRI_FAIL;  // the reference stops

@@ -1665,6 +1665,69 @@ int mcmcx_debug_symsvd(int32_t device, int32_t form, int32_t d, int32_t nmat, co
     return 0;
 }
 
+// The tick's factorisation on a caller's covariances: launch_factor, the function launch_adapt ends in, with mode 0 -- nothing about the
+// instances, grids or LDS sizes is restated here.  Everything is decided before the first write.
+int mcmcx_debug_calculate_R(mcmcx_handle h, const double *cmat, const uint8_t *need, int32_t *info_out, char *forms, int32_t len)
+{
+    const char *who = "mcmcx_debug_calculate_R";
+    if (!h || !cmat || !info_out) return fail(-57, std::string(who) + ": null argument");
+    if (!h->inited) return fail(-57, std::string(who) + ": the engine is not initialised");
+    if (h->pooled) return fail(-57, std::string(who) + ": not in pooled mode (the host factors the shared covariance)");
+    if (h->cfg.method == MCMCX_METHOD_RAM) return fail(-57, std::string(who) + ": not with method = 'ram' (no adaptation tick)");
+    if (!h->plan.am || !h->E.cmat) return fail(-57, std::string(who) + ": the engine has no adaptation state (doadapt = doburnin = 0)");
+    const AdaptPlan &a = h->plan.adapt;
+    const std::string post = a.post_name;
+    const std::string names = h->plan.svd_blocked ? post + ":1+" + a.svd.sweep_name + "+" + a.svd.applyv_name + "+" + post + ":2"
+        : a.factor ? post + ":3+" + a.factor_name : post;
+    if (forms && (len < 1 || (size_t)len <= names.size())) return fail(-57, std::string(who) + ": len too small for \"" + names + "\"");
+    const int d = h->d, P = h->P, n = h->cfg.nchains;
+    const size_t DD = (size_t)d * d;
+    std::vector<uint32_t> ic, flags0((size_t)h->nlanes);
+    std::vector<double> cm;
+    int rc;
+    if ((rc = fetch(h, h->E.ictr, (size_t)h->nlanes * NICTR, ic)) || (rc = fetch(h, h->E.cmat, (size_t)h->nlanes * P, cm))) return rc;
+    auto at = [&](int c, int k) -> uint32_t & { return ic[((size_t)(c / 64) * NICTR + k) * 64 + c % 64]; };
+    for (int c = 0; c < h->nlanes; ++c) {
+        const bool on = c < n && (!need || need[c]);
+        flags0[c] = at(c, I_ADFLAGS);
+        at(c, I_ADFLAGS) = on ? (uint32_t)ADF_DOCALC : 0u;
+        at(c, I_INFO) = (uint32_t)MCMCX_DEBUG_INFO_SENTINEL;
+        if (!on) continue;
+        const double *A = cmat + (size_t)c * DD;
+        for (int j = 0; j < d; ++j)
+            for (int i = 0; i <= j; ++i) cm[((size_t)(c / 64) * P + h_pidx(i, j, d)) * 64 + c % 64] = A[(size_t)i + (size_t)j * d];
+    }
+    HIPCHK(hipMemcpyAsync(h->E.cmat, cm.data(), cm.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->E.ictr, ic.data(), ic.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    launch_factor(h, 0, 0, 0);
+    HIPCHK(hipGetLastError());
+    if ((rc = fetch(h, h->E.ictr, (size_t)h->nlanes * NICTR, ic))) return rc;
+    for (int c = 0; c < n; ++c) info_out[c] = (int32_t)at(c, I_INFO);
+    for (int c = 0; c < h->nlanes; ++c) at(c, I_ADFLAGS) = flags0[c];
+    HIPCHK(hipMemcpyAsync(h->E.ictr, ic.data(), ic.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (forms) snprintf(forms, (size_t)len, "%s", names.c_str());
+    return 0;
+}
+
+// ... and the host's statement of it: host_initial_R, then host_potri on the scaled factor (initial_factor's sequence).  No device.
+int mcmcx_debug_host_calculate_R(int32_t d, const double *A, double *R_out, double *iC_out, int32_t *info_out)
+{
+    if (!A || !R_out || !info_out) return fail(-57, "mcmcx_debug_host_calculate_R: null argument");
+    if (d < 1 || d > 4096) return fail(-57, "mcmcx_debug_host_calculate_R: d outside 1 .. 4096");
+    const std::vector<double> cm(A, A + (size_t)d * d);
+    std::vector<double> Rp, Cp;
+    info_out[0] = host_initial_R(d, cm, Rp, Cp); info_out[1] = 0;
+    if (info_out[0] != 0) return 0;
+    std::vector<double> p = Rp;
+    unpack_upper(d, Rp, R_out, false);
+    if (!iC_out) return 0;
+    info_out[1] = host_potri(d, p);
+    if (info_out[1] == 0) unpack_upper(d, p, iC_out, false);
+    return 0;
+}
+
 int mcmcx_debug_math(int32_t op, int32_t n, const double *a, const double *b, double *out)
 {
     if (n < 1 || !a || !out) return fail(-1, "bad argument");

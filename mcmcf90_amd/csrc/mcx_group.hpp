@@ -1000,7 +1000,10 @@ __global__ __launch_bounds__(64 * NW) void tile_factor_kernel(EngineDev E)
         }
     }
     __syncthreads();
-    if (flg[cc]) {                                           // (a singular factor leaves the copy of R, as potri_packed does)
+    // (info2 != 0 cannot happen here: dpotf2 succeeded, every pivot was > 0, and a positive double's root times 2.4 / sqrt(npar) is not
+    // zero -- the smallest is 2.2e-162 x 2.4 / 8.  ST_POTRI_FAIL is the SVD factor's event, adapt_post_kernel<true, *>.  Could it occur
+    // here, the write-back below would still store the copy of R, triu(R), into iC: flg[] is dpotf2's verdict, not dpotri's.)
+    if (flg[cc]) {
         double *iCg = E.iC + (size_t)tile * P * 64 + cl0 + cc;
         const double *Mc = Mf + (size_t)cc * PS;
         for (int e = e0; e < P; e += CB * ES) {

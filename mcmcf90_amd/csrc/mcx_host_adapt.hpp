@@ -31,27 +31,13 @@ static void launch_svd(const SvdPlan &a, hipStream_t stream, double *Gc, double 
     hipLaunchKernelGGL(svd_finish_kernel, L, b256, 0, stream, Gc, Vc, svc, state, nlanes, d);
 }
 
-// Reads the plan (KernelPlan::adapt: the geometry and the kernel instantiations, chosen at mcmcx_init), it and mode -- nothing is
-// decided here but what the tick's mode decides.
-static void launch_adapt(mcmcx_engine *h, int it, int mode)
+// The factorisation's launches (MCMC_calculate_R for the chains with ADF_DOCALC, and with mode != 0 the covariance's bookkeeping in the
+// same kernel): the tail of the tick, and all of mcmcx_debug_calculate_R (mode 0: the bookkeeping rewrites what it read) -- one statement
+// of the instance choice, the grids and the LDS sizes the plan names.
+static void launch_factor(mcmcx_engine *h, int it, int mode, int batch_done)
 {
     const AdaptPlan &a = h->plan.adapt;
     const dim3 T(h->ntiles), b64(64), b256(256);
-    // the AP window (a batch recompute at every adaptation: no blocked update)
-    const bool ap = (mode & AD_AM) && h->cfg.adapthist > 1;
-    // covmat's batch branch in blocks (adapt_covb_*): the AP window; with initcmatn = 0 the first AM adaptation and the greedy restarts.
-    // Which lanes take it is the lanes' own business (ADF_BATCH); a tick that cannot hold any skips the launches.
-    const int batch_done = (h->plan.cov_batch &&
-                            (ap || (h->cfg.initcmatn == 0 && ((mode & AD_FIRST) || ((mode & AD_BURN) && h->cfg.greedy != 0))))) ? 1 : 0;
-    hipLaunchKernelGGL(adapt_pre_kernel, T, b64, 0, h->stream, h->E, it, mode);
-    if (batch_done) {
-        hipLaunchKernelGGL(adapt_covb_diag_kernel, dim3(a.g8 * a.n10), b64, 0, h->stream, h->E, it, a.n10);
-        if (a.noff > 0) hipLaunchKernelGGL(adapt_covb_off_kernel, dim3(a.g8 * a.noff), b64, 0, h->stream, h->E, it, a.noff);
-    }
-    if (!ap && !MCX_VARIANT_COV(h, a.g8, a.n10, a.noff, it, mode)) {
-        hipLaunchKernelGGL(adapt_cov_diag_kernel, dim3(a.g8 * a.n10), b64, 0, h->stream, h->E, it, mode, a.n10);
-        if (a.noff > 0) hipLaunchKernelGGL(adapt_cov_off_kernel, dim3(a.g8 * a.noff), b64, 0, h->stream, h->E, it, mode, a.noff);
-    }
     if (!h->plan.svd_blocked) {
         // the whole rest of the tick in adapt_post_kernel (phase 0) -- or, with tile_factor, its covariance bookkeeping (phase 3) and
         // dpotf2 (+ dtrti2 / dlauu2 with delayed rejection) on the packed matrices in LDS, read and written once (mcx_group.hpp)
@@ -69,6 +55,30 @@ static void launch_adapt(mcmcx_engine *h, int it, int mode)
     hipLaunchKernelGGL(chain2tile_kernel, tg, b256, 0, h->stream, h->d_Gc, h->E.Vw, DD, DD, h->d_need);
     hipLaunchKernelGGL(chain2tile_kernel, tg1, b256, 0, h->stream, h->d_svc, h->E.cs, (size_t)h->d, (size_t)2 * h->d, h->d_need);
     hipLaunchKernelGGL(a.post, T, b64, a.post_lds, h->stream, h->E, it, mode, 2, h->d_need, batch_done);
+}
+
+// Reads the plan (KernelPlan::adapt: the geometry and the kernel instantiations, chosen at mcmcx_init), it and mode -- nothing is
+// decided here but what the tick's mode decides.
+static void launch_adapt(mcmcx_engine *h, int it, int mode)
+{
+    const AdaptPlan &a = h->plan.adapt;
+    const dim3 T(h->ntiles), b64(64);
+    // the AP window (a batch recompute at every adaptation: no blocked update)
+    const bool ap = (mode & AD_AM) && h->cfg.adapthist > 1;
+    // covmat's batch branch in blocks (adapt_covb_*): the AP window; with initcmatn = 0 the first AM adaptation and the greedy restarts.
+    // Which lanes take it is the lanes' own business (ADF_BATCH); a tick that cannot hold any skips the launches.
+    const int batch_done = (h->plan.cov_batch &&
+                            (ap || (h->cfg.initcmatn == 0 && ((mode & AD_FIRST) || ((mode & AD_BURN) && h->cfg.greedy != 0))))) ? 1 : 0;
+    hipLaunchKernelGGL(adapt_pre_kernel, T, b64, 0, h->stream, h->E, it, mode);
+    if (batch_done) {
+        hipLaunchKernelGGL(adapt_covb_diag_kernel, dim3(a.g8 * a.n10), b64, 0, h->stream, h->E, it, a.n10);
+        if (a.noff > 0) hipLaunchKernelGGL(adapt_covb_off_kernel, dim3(a.g8 * a.noff), b64, 0, h->stream, h->E, it, a.noff);
+    }
+    if (!ap && !MCX_VARIANT_COV(h, a.g8, a.n10, a.noff, it, mode)) {
+        hipLaunchKernelGGL(adapt_cov_diag_kernel, dim3(a.g8 * a.n10), b64, 0, h->stream, h->E, it, mode, a.n10);
+        if (a.noff > 0) hipLaunchKernelGGL(adapt_cov_off_kernel, dim3(a.g8 * a.noff), b64, 0, h->stream, h->E, it, mode, a.noff);
+    }
+    launch_factor(h, it, mode, batch_done);
 }
 
 // Which branch of MCMC_adapt fires at iteration `it` (0 = none).  MCMC_adapt.F90:42-46, 60-61, 105.

@@ -66,6 +66,7 @@ struct AdaptPlan {
     // KernelPlan::tile_factor: tile_factor_kernel<NC, NW> -- 4 NW neighbouring chains' packed matrices in LDS
     void (*factor)(EngineDev) = nullptr; unsigned factor_grid = 0, factor_block = 0; size_t factor_lds = 0;
     SvdPlan svd;                                       // KernelPlan::svd_blocked
+    const char *post_name = "", *factor_name = "";     // the instances' names, for mcmcx_debug_calculate_R
 };
 // Which kernel forms the engine runs.  Decided ONCE, by plan_kernels at mcmcx_init (mcx_host_launch.hpp), from the configuration, the
 // problem's shape, the target kind, the switches and the CU count -- never from what was allocated; mcmcx_init allocates as it says and

@@ -521,10 +521,14 @@ static void plan_adapt(const mcmcx_engine *h, KernelPlan &p)
     if (xg) a.post_lds = 0;
     a.post = h->usesvd ? (xg ? adapt_post_kernel<true, true> : adapt_post_kernel<true, false>)
                        : (xg ? adapt_post_kernel<false, true> : adapt_post_kernel<false, false>);
+    a.post_name = h->usesvd ? (xg ? "adapt_post_kernel<true,true>" : "adapt_post_kernel<true,false>")
+                            : (xg ? "adapt_post_kernel<false,true>" : "adapt_post_kernel<false,false>");
     if (p.tile_factor) {
         const int nc = (d + 15) / 16, nw = nc <= 2 ? 4 : nc == 3 ? 2 : 1, ch = 4 * nw;
         a.factor = nc == 1 ? tile_factor_kernel<1, 4> : nc == 2 ? tile_factor_kernel<2, 4> : nc == 3 ? tile_factor_kernel<3, 2>
             : tile_factor_kernel<4, 1>;
+        a.factor_name = nc == 1 ? "tile_factor_kernel<1,4>" : nc == 2 ? "tile_factor_kernel<2,4>" : nc == 3 ? "tile_factor_kernel<3,2>"
+            : "tile_factor_kernel<4,1>";
         a.factor_block = (unsigned)(64 * nw);
         a.factor_lds = (size_t)ch * (h->P | 1) * sizeof(double) + (size_t)ch * sizeof(int);
         a.factor_grid = a.g8 * (unsigned)(64 / ch);

@@ -514,6 +514,19 @@ class Engine:
         self._chk(self.L.mcmcx_get_chaincov(self.h, chain, a.ctypes.data_as(C.POINTER(C.c_double)), _dp(m), C.byref(w)))
         return np.array(a), m, w.value
 
+    def debug_calculate_R(self, cmat, need=None):
+        """Test probe (mcmcx_debug_calculate_R): the tick's own factorisation on the covariances cmat[nchains, npar, npar] (symmetric), in
+        the instances this engine's plan chose.  Returns (info[nchains] -- INFO_SENTINEL where need == 0 --, forms); R, R2, iC, the status
+        and the covariance are read with R(), dr_state(), counters(), chaincov().  Raises McmcError on a refusal (-57)."""
+        a = np.ascontiguousarray(np.swapaxes(np.asarray(cmat, dtype=np.float64), 1, 2))
+        assert a.shape == (self.nchains, self.npar, self.npar), a.shape
+        nd = None if need is None else np.ascontiguousarray(np.asarray(need, dtype=np.uint8))
+        info = np.zeros(self.nchains, dtype=np.int32)
+        buf = C.create_string_buffer(256)
+        self._chk(self.L.mcmcx_debug_calculate_R(self.h, _dp(a), None if nd is None else nd.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 info.ctypes.data_as(C.POINTER(C.c_int32)), buf, 256))
+        return info, buf.value.decode()
+
     def accepted(self, chain=0):
         a = np.zeros(self.simuind, dtype=np.uint8)
         self._chk(self.L.mcmcx_get_accepted(self.h, chain, a.ctypes.data_as(C.POINTER(C.c_uint8))))
@@ -1008,6 +1021,24 @@ def debug_symsvd(form, A, need=None, device=0, fill=0.0, sweeps_fill=-1):
     if rc != 0:
         raise RuntimeError("mcmcx_debug_symsvd: %d %s" % (rc, (L.mcmcx_last_error() or b"").decode()))
     return np.swapaxes(V, 1, 2), s, sweeps, buf.value.decode()
+
+
+INFO_SENTINEL = -77          # MCMCX_DEBUG_INFO_SENTINEL
+
+
+def debug_host_calculate_R(A, with_inverse=True, fill=0.0):
+    """Test probe (mcmcx_debug_host_calculate_R): the host's host_initial_R + host_potri on the symmetric A[d, d], no device.  Returns
+    (R[d, d] upper, iC[d, d] upper, info, info2); what a failure leaves unwritten keeps `fill`.  Raises RuntimeError on a refusal."""
+    L = _lib.load()
+    A = np.asarray(A, dtype=np.float64)
+    d = A.shape[-1]
+    a = np.ascontiguousarray(A.T)
+    R = np.full((d, d), fill); iC = np.full((d, d), fill)
+    info = np.zeros(2, dtype=np.int32)
+    rc = L.mcmcx_debug_host_calculate_R(d, _dp(a), _dp(R), _dp(iC) if with_inverse else None, info.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise RuntimeError("mcmcx_debug_host_calculate_R: %d %s" % (rc, (L.mcmcx_last_error() or b"").decode()))
+    return R.T.copy(), iC.T.copy(), int(info[0]), int(info[1])
 
 
 def engine_from_problem(cfg_kw, prob_kw, nchains=1, **extra):

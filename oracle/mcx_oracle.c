@@ -237,6 +237,13 @@ int mcxo_potri_u(int n, double *A)
 
 int mcxo_symsvd(int n, double *G, double *V, double *s) { return mcxs_symsvd(n, G, V, s); }
 
+/* out[i] = fma(a[i], b[i], c[i]): the one rounding primitive numpy lacks, for the tests' numpy restatements (tests/factor_ref.py),
+ * which keep the order of operations, the skips and the pivot tests to themselves.  out may be c. */
+void mcxo_fma_v(int n, const double *a, const double *b, const double *c, double *out)
+{
+    for (int i = 0; i < n; ++i) out[i] = fma(a[i], b[i], c[i]);
+}
+
 /* dgemv (matutils.F90:161, matmulx), alpha = 1, beta = 0, netlib 3.8.0 loop order with fma accumulation:
  * 'N': y = 0; for j: temp = x(j); y(i) += temp*a(i,j).   'T': y(j) = sum_i a(i,j) x(i), i ascending. */
 void mcxo_gemv(int trans, int n, const double *A, const double *x, double *y)

@@ -140,6 +140,7 @@ void mcxo_covmat(int n, int p, const double *x, int ldx, const double *w, int nw
                  double *cmat, double *xmean, double *wsum, int update);
 int  mcxo_calculate_R(mcxo_chain *c, double *cmat);
 int  mcxo_symsvd(int n, double *G, double *V, double *s);      /* pinned dgesvd('A','N') of a PSD matrix, mcx_svd.h */
+void mcxo_fma_v(int n, const double *a, const double *b, const double *c, double *out);   /* element-wise fma, for numpy restatements */
 void mcxo_gemv(int trans, int n, const double *A, const double *x, double *y);   /* y = A x or A'x, netlib dgemv order */
 double mcxo_log(double x);
 double mcxo_exp(double x);

@@ -99,6 +99,10 @@ def lib():
         L.mcxo_chdd.restype = C.c_int
         L.mcxo_symsvd.argtypes = [C.c_int, _DP, _DP, _DP]
         L.mcxo_symsvd.restype = C.c_int
+        L.mcxo_calculate_R.argtypes = [C.POINTER(Chain), _DP]
+        L.mcxo_calculate_R.restype = C.c_int
+        L.mcxo_fma_v.argtypes = [C.c_int, _DP, _DP, _DP, _DP]
+        L.mcxo_fma_v.restype = None
         L.mcxo_gemv.argtypes = [C.c_int, C.c_int, _DP, _DP, _DP]
         L.mcxo_covmat.argtypes = [C.c_int, C.c_int, _DP, C.c_int, _DP, C.c_int, _DP, _DP, _DP, C.c_int]
         L.mcxo_alpha.argtypes = [C.c_double] * 5
@@ -218,6 +222,40 @@ def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_dow
         r.rng_n = c.rng.n
         r.rng_saved, r.rng_saved_y = c.rng.saved, c.rng.saved_y
         r.ram_downdate_fail = c.ram_downdate_fail
+        return r
+    finally:
+        L.mcxo_chain_free(ch)
+
+
+def calculate_R(cfg, cmat, cmat0=None):
+    """MCMC_calculate_R (mcxo_calculate_R) on the symmetric cmat[n, n] for a configuration: a chain is created on a Gaussian target from
+    cmat0 (default: the identity), so that R, R2 and iC hold what an engine holds before its first tick, then the routine is called once.
+    Returns a Result with R, R2, iC (as [i, j]; R2 and iC only with delayed rejection), cmat (rewritten when the SVD branch floored
+    the singular values: floored = 1), info (0, dpotf2's pivot, n for a zero largest singular value, -2000 - info2 when dpotri found a
+    zero on the diagonal) and R_before, R2_before, iC_before."""
+    L = lib()
+    cmat = f64(cmat)
+    n = cmat.shape[0]
+    prob = Problem("gauss", n, np.zeros(n), np.eye(n) if cmat0 is None else cmat0, mu=np.zeros(n), lam=np.eye(n))
+    tgt = prob.ctarget()
+    cm0 = np.asfortranarray(prob.cmat0)
+    ch = L.mcxo_chain_create_ny(C.byref(cfg), C.byref(tgt), _dp(prob.par0), cm0.ctypes.data_as(_DP), _dp(prob.sigma2v),
+                                prob.nobsv.ctypes.data_as(C.POINTER(C.c_int)), prob.ny, 1, 0)
+    if not ch:
+        raise RuntimeError("could not factor the initial covariance")
+    try:
+        c = ch.contents
+        get = lambda p: np.ctypeslib.as_array(p, shape=(n, n)).T.copy()
+        r = Result()
+        r.R_before = get(c.R)
+        if cfg.dodr:
+            r.R2_before, r.iC_before = get(c.R2), get(c.iC)
+        work = np.asfortranarray(cmat.copy())
+        r.info = int(L.mcxo_calculate_R(ch, work.ctypes.data_as(_DP)))
+        r.R = get(c.R)
+        if cfg.dodr:
+            r.R2, r.iC = get(c.R2), get(c.iC)
+        r.cmat, r.floored = np.array(work), int(c.svd_floored)
         return r
     finally:
         L.mcxo_chain_free(ch)
