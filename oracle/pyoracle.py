@@ -176,9 +176,14 @@ class Result:
     pass
 
 
-def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_downdate_fail=False, scam_fast=False):
+def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_downdate_fail=False, scam_fast=False, marks=()):
     """Run one chain through the oracle; returns the reference-visible outputs.
-    scam_fast (method = 'scam'): the engine's opt-in componentwise proposal oldpar + zj U(:,j), mcx_oracle.h."""
+    scam_fast (method = 'scam'): the engine's opt-in componentwise proposal oldpar + zj U(:,j), mcx_oracle.h.
+    marks: ascending iterations at which the run pauses (mcxo_chain_run resumes where it stopped, like LiveChain.run) and notes
+    (stayed, drtries, draccepted, n_calcR, info_last) in r.marks[k]; r.chol_failed says whether a MCMC_calculate_R between two notes (or
+    between the last and the end) reported info != 0 -- what the engine keeps as the sticky status bit ST_CHOL_FAIL.  info_last is the LAST
+    call's: chol_failed is the engine's bit only when marks holds every tick (at most one MCMC_calculate_R between two notes).  With marks = ()
+    it says no more than whether the last factorisation of the whole run failed."""
     L = lib()
     tgt = prob.ctarget()
     cm = np.asfortranarray(prob.cmat0)            # column-major like the reference
@@ -189,11 +194,19 @@ def run_chain(cfg, prob, seed=0x6D636D63, chain_id=0, upto=None, continue_on_dow
     try:
         ch.contents.continue_on_downdate_fail = 1 if continue_on_downdate_fail else 0
         ch.contents.scam_fast = 1 if scam_fast else 0
-        rc = L.mcxo_chain_run(ch, cfg.nsimu if upto is None else upto)
+        end = cfg.nsimu if upto is None else upto
         c = ch.contents
+        rc, noted, ncalc, failed = 0, [], c.n_calcR, False
+        for it in list(marks) + [end]:
+            if rc == 0 and it <= end:
+                rc = L.mcxo_chain_run(ch, it)
+                failed = failed or (c.n_calcR != ncalc and c.info_last != 0)
+                ncalc = c.n_calcR
+                noted.append((c.stayed, c.drtries, c.draccepted, c.n_calcR, c.info_last))
         n, ns = prob.npar, c.simuind
         r = Result()
         r.rc = rc
+        r.marks, r.chol_failed = np.array(noted[:-1], dtype=np.int64).reshape(-1, 5), failed
         r.simuind, r.chainind = c.simuind, c.chainind
         r.chain = np.ctypeslib.as_array(c.chain, shape=(cfg.nsimu, n + 1))[:c.chainind].copy()
         ny = prob.ny

@@ -136,6 +136,23 @@ def _problem(prob):
 _ORACLE = {}
 
 
+def _pack(rs, nch, d, nsimu):
+    """What the comparison needs of a problem's oracle chains, as read-only arrays over the chains."""
+    assert len(rs) == nch and all(r.simuind == nsimu and r.rc == 0 for r in rs)
+    o = dict(theta=np.array([r.theta for r in rs]), acc=np.array([r.accepted for r in rs], dtype=np.uint8),
+             scal=np.array([[r.ss1, r.sspri1, r.sigma2, r.alpha12] for r in rs]), rng=np.array([r.rng_n for r in rs], dtype=np.uint64),
+             ctr=np.array([[r.stayed, r.bndstayed, r.drtries, r.draccepted, r.erstayed] for r in rs], dtype=np.int64),
+             nprop=np.array([r.nprop for r in rs], dtype=np.int64), ssinf=np.array([r.n_ss_inf for r in rs], dtype=np.int64),
+             ssnan=np.array([r.n_ss_nan for r in rs], dtype=np.int64),
+             R=np.array([r.R for r in rs]), qstd=np.array([r.qcovstd for r in rs]), R2=np.array([r.R2 for r in rs]), iC=np.array([r.iC for r in rs]),
+             cmat=np.array([r.chaincmat for r in rs]), mean=np.array([r.chainmean for r in rs]), wsum=np.array([r.chainwsum for r in rs]),
+             alpha=np.array([r.alpha for r in rs]), ss1v=np.array([r.ss1v for r in rs]), s2chain=np.array([r.s2chain for r in rs]).reshape(nch, nsimu, -1))
+    assert o["theta"].shape == (nch, d) and o["acc"].shape == (nch, nsimu) and o["R"].shape == o["cmat"].shape == (nch, d, d)
+    for v in o.values():
+        v.setflags(write=False)
+    return o
+
+
 def _oracle_all(oracle, prob):
     """Every chain of a problem through the oracle: computed once per problem (the forms that share a problem share it), never changed.
     (The oracle keeps no state outside a chain: eight chains at a time.)"""
@@ -146,19 +163,7 @@ def _oracle_all(oracle, prob):
         oracle.lib()
         with ThreadPoolExecutor(8) as pool:
             rs = list(pool.map(lambda c: oracle.run_chain(cfg, pr, chain_id=CHAIN_ID0 + c, scam_fast=bool(_fast(prob))), range(nch)))
-        assert len(rs) == nch and all(r.simuind == nsimu and r.rc == 0 for r in rs)
-        o = dict(theta=np.array([r.theta for r in rs]), acc=np.array([r.accepted for r in rs], dtype=np.uint8),
-                 scal=np.array([[r.ss1, r.sspri1, r.sigma2, r.alpha12] for r in rs]), rng=np.array([r.rng_n for r in rs], dtype=np.uint64),
-                 ctr=np.array([[r.stayed, r.bndstayed, r.drtries, r.draccepted, r.erstayed] for r in rs], dtype=np.int64),
-                 nprop=np.array([r.nprop for r in rs], dtype=np.int64), ssinf=np.array([r.n_ss_inf for r in rs], dtype=np.int64),
-                 ssnan=np.array([r.n_ss_nan for r in rs], dtype=np.int64),
-                 R=np.array([r.R for r in rs]), qstd=np.array([r.qcovstd for r in rs]), R2=np.array([r.R2 for r in rs]), iC=np.array([r.iC for r in rs]),
-                 cmat=np.array([r.chaincmat for r in rs]), mean=np.array([r.chainmean for r in rs]), wsum=np.array([r.chainwsum for r in rs]),
-                 alpha=np.array([r.alpha for r in rs]), ss1v=np.array([r.ss1v for r in rs]), s2chain=np.array([r.s2chain for r in rs]).reshape(nch, nsimu, -1))
-        assert o["theta"].shape == (nch, d) and o["acc"].shape == (nch, nsimu) and o["R"].shape == o["cmat"].shape == (nch, d, d)
-        for v in o.values():
-            v.setflags(write=False)
-        _ORACLE[prob] = o
+        _ORACLE[prob] = _pack(rs, nch, d, nsimu)
     return _ORACLE[prob]
 
 
@@ -359,15 +364,25 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     cols = prob[0] == "cols"                                    # (the recorded chain is the engine's only view of the second column)
     e = engine_from_problem(ckw, pkw, nchains=nch, chain_id0=CHAIN_ID0, record_accept=1, record_chain=1 if cols else 0, scam_fast=_fast(prob))
     e.init()
+    failures = _run_and_compare(e, o, ckw, nch, cuts, kernel, edge="edge" in dict(prob[2]), cols=cols)
+    assert not failures, "; ".join(failures)
+
+
+def _run_and_compare(e, o, ckw, nch, cuts, kernel, edge=False, cols=False):
+    """Run an initialised engine through the cuts, asserting the kernel after each; read every chain, close the engine, and compare every quantity
+    on every chain with the oracle's (_pack).  Returns one line per quantity that differs, with the first failing chains.  (tests/test_gpu_accept_extremes.py
+    runs its chains through this too: there o carries the expected status bits, and method = 'ram' keeps no covariance.)"""
+    nsimu, ram = ckw["nsimu"], ckw["method"] == "ram"
     for upto in cuts:
         e.run(upto)
         assert e.last_kernel() == kernel, e.last_kernel()
     assert e.simuind == nsimu
     theta, masks, scal = e.theta(), e.accept_masks(), e.scalars()
     rng = np.array([e.rng(c)[0] for c in range(nch)], dtype=np.uint64)
-    ctr = np.array([[k[n] for n in ("stayed", "bndstayed", "drtries", "draccepted", "erstayed")] for k in (e.counters(c) for c in range(nch))], dtype=np.int64)
+    ctr = np.array([[k[n] for n in ("stayed", "bndstayed", "drtries", "draccepted", "erstayed", "status")] for k in (e.counters(c) for c in range(nch))], dtype=np.int64)
+    ctr, status = ctr[:, :5], ctr[:, 5]
     R = np.array([e.R(c) for c in range(nch)])
-    cov = [e.chaincov(c) for c in range(nch)]
+    cov = None if ram else [e.chaincov(c) for c in range(nch)]
     qstd = np.array([e.qcovstd(c) for c in range(nch)]) if ckw["method"] == "scam" else None
     dr = [e.dr_state(c) for c in range(nch)] if ckw["drscale"] else None
     rec = [e.chain(c) for c in range(nch)] if cols else None
@@ -377,7 +392,7 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     acc = ((masks[:, c // 64] >> (c % 64).astype(np.uint64)) & np.uint64(1)).astype(np.uint8).T         # [chain][iteration]
     # no chain is left out
     assert acc.shape == o["acc"].shape and theta.shape == o["theta"].shape and scal.shape == o["scal"].shape and R.shape == o["R"].shape
-    assert rng.shape == o["rng"].shape and ctr.shape == o["ctr"].shape and len(cov) == nch and (dr is None or len(dr) == nch)
+    assert rng.shape == o["rng"].shape and ctr.shape == o["ctr"].shape and (cov is None or len(cov) == nch) and (dr is None or len(dr) == nch)
 
     full = ckw["method"] == "scam" or ckw.get("condmax", 0.0) > 0.0     # an SVD factor is a full matrix
     tri = (lambda a: a) if full else (lambda a: np.triu(a))
@@ -397,16 +412,19 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     for j, name in enumerate(("ss1", "sspri1", "sigma2", "alpha12")):
         if name != "alpha12" or ckw["method"] != "er":          # (MCMC_run_er computes no alpha)
             # (a NaN only where one can legitimately be, in the edge cases: alpha12, and ss1 under early rejection, which accepts a NaN proposal)
-            check(name, scal[:, j], o["scal"][:, j], nan_ok="edge" in dict(prob[2]) and (name == "alpha12" or (name == "ss1" and ckw["method"] == "er")))
+            check(name, scal[:, j], o["scal"][:, j], nan_ok=edge and (name == "alpha12" or (name == "ss1" and ckw["method"] == "er")))
     check("stream position", rng, o["rng"])
     for j, name in enumerate(("stayed", "bndstayed", "drtries", "draccepted", "erstayed")):
         check(name, ctr[:, j], o["ctr"][:, j])
+    if "status" in o:
+        check("status bits", status, o["status"])
     check("R", np.array([tri(a) for a in R]), np.array([tri(a) for a in o["R"]]))
     if qstd is not None:
         check("qcovstd", qstd, o["qstd"])
-    check("chaincmat", np.array([np.triu(k[0]) for k in cov]), np.array([np.triu(a) for a in o["cmat"]]))
-    check("chainmean", np.array([k[1] for k in cov]), o["mean"])
-    check("chainwsum", np.array([k[2] for k in cov]), o["wsum"])
+    if cov is not None:
+        check("chaincmat", np.array([np.triu(k[0]) for k in cov]), np.array([np.triu(a) for a in o["cmat"]]))
+        check("chainmean", np.array([k[1] for k in cov]), o["mean"])
+        check("chainwsum", np.array([k[2] for k in cov]), o["wsum"])
     if rec is not None:                                         # one ss and one sigma2 per response column
         ny = o["ss1v"].shape[1]
         assert ny == 2 and len(rec) == nch
@@ -415,4 +433,4 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     if dr is not None:
         check("R2", np.array([tri(k[0]) for k in dr]), np.array([tri(a) for a in o["R2"]]))
         check("iC", np.array([np.triu(k[1]) for k in dr]), np.array([np.triu(a) for a in o["iC"]]))
-    assert not failures, "; ".join(failures)
+    return failures

@@ -7,6 +7,9 @@ one that two forms share.  Here 583 chains (nine full tiles and seven chains: a 
 chains) run 150 iterations from cmat0 = inv(lam), where the chain sits near alphatarget and most iterations downdate, cut as
 run(60), run(61), run(); and EVERY chain's state, accept sequence, factor, stream position, counters and status bit must be the
 oracle's (MCMC_run_ram.F90:45-179, dchud.f:122-139, dchdd.f:141-179), bit for bit."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import pytest
 
@@ -81,8 +84,12 @@ def _oracle_all(oracle, kernel, d, edge=None):
         o = dict(theta=np.zeros((NCH, d)), acc=np.zeros((NCH, NSIMU), dtype=np.uint8), R=np.zeros((NCH, d, d)), rng=np.zeros(NCH, dtype=np.uint64),
                  stayed=np.zeros(NCH, dtype=np.int64), bndstayed=np.zeros(NCH, dtype=np.int64), fail=np.zeros(NCH, dtype=bool),
                  scal=np.zeros((NCH, 4)), ssinf=np.zeros(NCH, dtype=np.int64), ssnan=np.zeros(NCH, dtype=np.int64), nprop=np.zeros(NCH, dtype=np.int64))
-        for c in range(NCH):
-            r = oracle.run_chain(cfg, prob, chain_id=CHAIN_ID0 + c, continue_on_downdate_fail=True)
+        oracle.lib()
+        # (the oracle keeps no state outside a chain and ctypes releases the GIL: a thread pool, as in tests/test_gpu_every_chain.py)
+        with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:
+            rs = list(pool.map(lambda c: oracle.run_chain(cfg, prob, chain_id=CHAIN_ID0 + c, continue_on_downdate_fail=True), range(NCH)))
+        assert len(rs) == NCH
+        for c, r in enumerate(rs):
             assert r.simuind == NSIMU
             o["theta"][c], o["acc"][c], o["R"][c], o["rng"][c] = r.theta, r.accepted, r.R, r.rng_n
             o["stayed"][c], o["bndstayed"][c], o["fail"][c] = r.stayed, r.bndstayed, r.ram_downdate_fail != 0
