@@ -737,6 +737,9 @@ __global__ __launch_bounds__(64, 1) void adapt_cov_off_kernel(EngineDev E, int i
 #endif
 // XG (npar > 320: one npar-vector per lane no longer fits a CU's LDS): the work vector in the tile's global scratch (EngineDev::xscr) -- a
 // compile-time choice, so that neither form uses flat accesses.  Slower; any npar.
+// Its LDS (not XG): ONE work vector X [max(npar, 36)][64] doubles -- the npar-vector of covmat_rows / potri_packed, or the 28 + 8 vectors
+// of calculate_R's diagonal block (18 kB: eight waves per CU up to npar 36)
+MCX_HD size_t adapt_post_lds(int d) { return (size_t)(d > 36 ? d : 36) * 64 * sizeof(double); }
 template <bool SVD, bool XG = false>
 __global__ __launch_bounds__(64, SVD ? 1 : MCX_POST_WAVES) void adapt_post_kernel(EngineDev E, int it, int mode, int phase, uint8_t *need,
     int batch_done)

@@ -1307,11 +1307,11 @@ static int pooled_moments_launch(mcmcx_engine *h, double *dev_dst, int kind, int
     HIPCHK(hipSetDevice(h->cfg.device));
     const int len = pooled_vec_len(h, kind), T = h->ntiles;
     const double rs = (kind == 2) ? 1.0 / std::pow((double)(float)it, h->cfg.nuparam) : 0.0;      // like d_ramscale (MCMC_run_ram.F90:166)
-    const size_t mlds = ((size_t)64 * (h->d | 1) + 320) * sizeof(double);
-    if (mlds <= 160 * 1024) hipLaunchKernelGGL(moments_kernel<false>, dim3(T), dim3(256), mlds, h->stream, h->E, h->d_moments,
+    const size_t mlds = MomentsLds(h->d, false).bytes;
+    if (mlds <= LDS_PER_CU) hipLaunchKernelGGL(moments_kernel<false>, dim3(T), dim3(256), mlds, h->stream, h->E, h->d_moments,
         h->cfg.nchains, kind, it, rs);
     // npar >= 316: (64 (d | 1) + 320) 8 bytes exceed 160 KiB (317: 164 864)
-    else hipLaunchKernelGGL(moments_kernel<true>, dim3(T), dim3(256), (size_t)320 * sizeof(double), h->stream, h->E, h->d_moments,
+    else hipLaunchKernelGGL(moments_kernel<true>, dim3(T), dim3(256), MomentsLds(h->d, true).bytes, h->stream, h->E, h->d_moments,
         h->cfg.nchains, kind, it, rs);
     moments_tree_launch(h->stream, h->d_moments, T, len, dev_dst);
     HIPCHK(hipGetLastError());

@@ -8,6 +8,8 @@
 
 namespace mcx {
 
+// LDS of a gfx950 CU: what a kernel's dynamic-LDS layout may take, and what the "waves per CU" rules of plan_kernels divide
+constexpr size_t LDS_PER_CU = 160 * 1024;
 
 // EXPCOLS / MODULE: host side only (the device sees TGT_HOST + an evaluation kernel between the phases)
 enum { TGT_GAUSS = 0, TGT_BANANA = 1, TGT_EXPDATA = 2, TGT_HOST = 3, TGT_EXPCOLS = 4, TGT_MODULE = 5 };

@@ -13,6 +13,8 @@
 namespace mcx {
 
 #define MCX_DEV __device__ __forceinline__
+// a kernel's LDS layout: the kernel takes its pointers from it, the launch its bytes
+#define MCX_HD __host__ __device__ __forceinline__
 
 // ---------------------------------------------------------------- bits
 MCX_DEV int32_t hi32(double x) { return __double2hiint(x); }

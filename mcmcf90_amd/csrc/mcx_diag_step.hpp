@@ -45,6 +45,13 @@ constexpr int diag_step_waves(int W) { return W == 1 ? 8 : W == 9 ? 4 : W == 17 
 
 // diag_tile_kernel<W> of u_f(x): the same grid, the same argument block; ekey[nfields][nbins + 1] and table[nfields][nbins + 2] behind
 // it.  Dynamic LDS: 4 (2 nbins + 3) words of 64 bits.  Every wave passes the barrier before one without a field leaves.
+// Its LDS, per wave (four of them): ek [nbins + 1] keys | tb [nbins + 2] table values, words of 64 bits all
+struct DiagStepLds {
+    int tb;                                                         // behind the wave's ek; in words
+    size_t wave, bytes;                                             // a wave's stride
+    MCX_HD explicit DiagStepLds(int nbins) : tb(nbins + 1), wave((size_t)(tb + (nbins + 2))),
+        bytes(4 * wave * sizeof(unsigned long long)) {}
+};
 template <int W>
 __global__ __launch_bounds__(256, diag_step_waves(W)) void diag_step_tile_kernel(DiagArgs A, const unsigned long long *__restrict__ ekey,
     const double *__restrict__ table, int nbins)
@@ -55,6 +62,7 @@ __global__ __launch_bounds__(256, diag_step_waves(W)) void diag_step_tile_kernel
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ne = nbins + 1, nc = nbins + 2;
     const size_t tile = blockIdx.x;
     const int f = (int)blockIdx.y * 4 + wave;
+    // DiagStepLds, spelled out (taking the offsets from it moves an instruction of every instance)
     unsigned long long *ek = step_lds + (size_t)wave * (size_t)(ne + nc);
     double *tb = (double *)(ek + ne);
     if (f < A.nfields) {

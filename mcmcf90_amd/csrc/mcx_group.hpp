@@ -828,7 +828,14 @@ __global__ void group_check_kernel(EngineDev E, int *flag)
 // adapt_post_kernel streamed the packed matrices of a tile ~5.6 times through L2 / HBM for its 8 x 8 register blocks (33.5 ms per tick of
 // 1 048 576 chains at npar 50, 2.2 ms at config 3's size); this reads and writes each once.  Results: R, R2, iC, I_INFO and the status
 // bits, as adapt_post_kernel leaves them.  (Round 4's one-wave form with [row][column] squares in LDS, group_factor_kernel, is superseded:
-// tools/variants/README.md.) Grid: 8 ceil(ntiles / 8) (64 / (4 NW)) workgroups of 64 NW threads; LDS: 4 NW (P | 1) doubles + 4 NW ints.
+// tools/variants/README.md.) Grid: 8 ceil(ntiles / 8) (64 / (4 NW)) workgroups of 64 NW threads.
+// Its LDS: M [CH][PS] doubles, the packed triangles of the workgroup's CH = 4 NW chains at the odd stride PS = P | 1 | flg [CH] ints
+struct TileFactorLds {
+    int PS;
+    size_t flg, bytes;                                              // (M at 0; flg in doubles)
+    MCX_HD TileFactorLds(int P, int NW) : PS(P | 1), flg((size_t)(4 * NW) * PS),
+        bytes(flg * sizeof(double) + (size_t)(4 * NW) * sizeof(int)) {}
+};
 template <int NC, int NW>
 __global__ __launch_bounds__(64 * NW) void tile_factor_kernel(EngineDev E)
 {
@@ -839,11 +846,13 @@ __global__ __launch_bounds__(64 * NW) void tile_factor_kernel(EngineDev E)
     const int tile = (idx / WPT) * 8 + xcd, part = idx % WPT;
     if (tile >= E.ntiles) return;                                          // (uniform over the workgroup)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l16 = lane & 15, row = lane >> 4;
-    const int d = E.d, P = E.P, PS = P | 1;
+    const int d = E.d, P = E.P;
+    const TileFactorLds lds(P, NW);
+    const int PS = lds.PS;
     const int cl0 = part * CH, cl = cl0 + 4 * w + row;                      // this lane's chain of the tile
     // its packed upper triangle: element (i,k), i <= k, at i d - i (i + 1) / 2 + k
     double *M = Mf + (size_t)(4 * w + row) * PS;
-    int *flg = (int *)(Mf + (size_t)CH * PS);
+    int *flg = (int *)(Mf + lds.flg);
     const bool act = (TIDX(E.ictr, tile, NICTR, I_ADFLAGS, cl) & ADF_DOCALC) != 0;
     if (!__syncthreads_or(act ? 1 : 0)) return;
     // cooperative moves: chain cc of the workgroup, elements e0, e0 + ES, ...

@@ -45,12 +45,21 @@ MCX_DEV int hist_cell(const unsigned long long *ek, int ne, int top, unsigned lo
 // grid (gx, nfields, gz), 256 threads, dynamic LDS: nbins + 1 keys of 64 bits, then nbins + 2 counters of 32 bits.  The block's four
 // waves take tiles 4 bx + w, + 4 gx, ..; blockIdx.z takes window samples z chunk .. (z + 1) chunk - 1.  One LDS atomic per value: the
 // values of a field that has converged spread over the bins, so the lanes of a wave mostly hit different counters.
+// hist_kernel's LDS: ek [nbins + 1] keys of 64 bits | cnt [nbins + 2] counters of 32 bits; hist2_kernel's (pair = true): ekj [nbins + 1] |
+// ekk [nbins + 1] | cnt [(nbins + 2)**2].  Offsets in words of 64 bits
+struct HistLds {
+    int ekk, cnt;                                                   // (ek / ekj at 0)
+    size_t bytes;
+    MCX_HD HistLds(int nbins, bool pair) : ekk(pair ? nbins + 1 : 0), cnt(pair ? 2 * (nbins + 1) : nbins + 1),
+        bytes((size_t)cnt * sizeof(unsigned long long) + (size_t)(nbins + 2) * (size_t)(pair ? nbins + 2 : 1) * sizeof(unsigned int)) {}
+};
 __global__ __launch_bounds__(256) void hist_kernel(QuantWin A, const unsigned long long *__restrict__ ekey, unsigned long long *out,
     int nbins, int top)
 {
     extern __shared__ unsigned long long hist_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ne = nbins + 1, nc = nbins + 2;
     const int f = blockIdx.y;
+    // HistLds(nbins, false), spelled out (taking the offset from it moves this kernel's instructions)
     unsigned long long *ek = hist_lds;
     unsigned int *cnt = (unsigned int *)(hist_lds + ne);
     for (int i = threadIdx.x; i < ne; i += 256) ek[i] = ekey[(size_t)f * (size_t)ne + (size_t)i];
@@ -92,8 +101,9 @@ __global__ __launch_bounds__(256) void hist2_kernel(QuantWin A, const unsigned l
     constexpr int LB = HIST_LB / 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ne = nbins + 1, nc = nbins + 2;
     const int fj = P.j[blockIdx.y], fk = P.k[blockIdx.y];
-    unsigned long long *ekj = hist_lds, *ekk = hist_lds + ne;
-    unsigned int *cnt = (unsigned int *)(hist_lds + 2 * ne);
+    const HistLds lds(nbins, true);
+    unsigned long long *ekj = hist_lds, *ekk = hist_lds + lds.ekk;
+    unsigned int *cnt = (unsigned int *)(hist_lds + lds.cnt);
     for (int i = threadIdx.x; i < ne; i += 256) {
         ekj[i] = ekey[(size_t)fj * (size_t)ne + (size_t)i];
         ekk[i] = ekey[(size_t)fk * (size_t)ne + (size_t)i];

@@ -108,7 +108,7 @@ static void launch_pooled_lane(mcmcx_engine *h, int itA)
 template <int PA, bool STAGE2>
 static void launch_pooled_mfma(mcmcx_engine *h, int itA, int itB)
 {
-    const size_t lds = std::max((size_t)((h->d + 3) & ~3) * 64 * sizeof(double), PA == 2 ? lds_step(h) : (size_t)0);
+    const size_t lds = pooled_phase_mfma_lds(h->d, PA == 2 && h->plan.dr_lds);
     hipLaunchKernelGGL((pooled_phase_mfma_kernel<PA, STAGE2>), dim3(h->ntiles), dim3(64), lds, h->stream, h->E, itA, itB,
         (const double *)h->d_ramscale, (const double *)(STAGE2 ? h->pool.d_R2T : h->pool.d_RT), (const double *)h->pool.d_iC,
         h->cfg.method == MCMCX_METHOD_RAM ? 1 : 0);

@@ -51,7 +51,7 @@ static int diag_step_launch(const SampleWin &W, double *w, int maxlag, int nbins
     if (shift) HIPCHK(hipMemcpyAsync(dshift, shift, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, stream));
     else hipLaunchKernelGGL(diag_step_shift_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, W.store, ek, tb, dshift,
         W.slot0, W.ntiles, nf, nbins);
-    const size_t lds = 4 * (size_t)(ne + nc) * sizeof(unsigned long long);
+    const size_t lds = DiagStepLds(nbins).bytes;
     diag_with_W(A.K, [&](auto w_) {
         hipLaunchKernelGGL(diag_step_tile_kernel<decltype(w_)::value>, diag_grid(A), dim3(256), lds, stream, A, ek, tb, nbins);
     });

@@ -88,7 +88,7 @@ static QuantWin hist_window(const SampleWin &W, int chunk)
 static int hist_launch(const QuantWin &A, unsigned long long *wkeys, int nbins, const double *edges, int npairs, const int32_t *pairs,
                        unsigned long long *dev_out, hipStream_t stream)
 {
-    const int nf = A.win.nfields, T = A.win.ntiles, ne = nbins + 1, nc = nbins + 2, ny = npairs ? npairs : nf;
+    const int nf = A.win.nfields, T = A.win.ntiles, ne = nbins + 1, ny = npairs ? npairs : nf;
     const size_t words = hist_table_words(nf, npairs, nbins);
     int rc = samples_stage_keys(wkeys, edges, hist_key_words(nf, nbins), stream); if (rc) return rc;
     int top = 1;
@@ -99,13 +99,11 @@ static int hist_launch(const QuantWin &A, unsigned long long *wkeys, int nbins, 
     const unsigned long long *ek = wkeys;
     hipLaunchKernelGGL(quant_counts_zero_kernel, dim3((unsigned)((words + 255) / 256)), block, 0, stream, dev_out, (int)words);
     if (!npairs) {
-        const size_t lds = (size_t)ne * sizeof(unsigned long long) + (size_t)nc * sizeof(unsigned int);
-        hipLaunchKernelGGL(hist_kernel, grid, block, lds, stream, A, ek, dev_out, nbins, top);
+        hipLaunchKernelGGL(hist_kernel, grid, block, HistLds(nbins, false).bytes, stream, A, ek, dev_out, nbins, top);
     } else {
         HistPairs P;
         for (int p = 0; p < HIST2_MAXPAIRS; ++p) { P.j[p] = p < npairs ? pairs[2 * p] : 0; P.k[p] = p < npairs ? pairs[2 * p + 1] : 0; }
-        const size_t lds = 2 * (size_t)ne * sizeof(unsigned long long) + (size_t)nc * (size_t)nc * sizeof(unsigned int);
-        hipLaunchKernelGGL(hist2_kernel, grid, block, lds, stream, A, ek, P, dev_out, nbins, top);
+        hipLaunchKernelGGL(hist2_kernel, grid, block, HistLds(nbins, true).bytes, stream, A, ek, P, dev_out, nbins, top);
     }
     HIPCHK(hipGetLastError());
     return 0;

@@ -4,14 +4,12 @@
 // Part of the ONE translation unit mcx_api.hip (included there, in this order: mcx_host_engine, mcx_host_linalg, mcx_host_launch,
 // mcx_host_adapt, mcx_host_pooled, mcx_host_callbacks); not a stand-alone header.
 
-// LDS of pooled_mfma_kernel: the tile's vector [d4][64] (+ the products [16 nt][64] when they need more than one pass)
-// and the partial ss chains [4 nt][64]
-static size_t pooled_mfma_lds(int d)
+// (the bytes of dynamic LDS a launch passes come from the kernel's own layout, stated next to the kernel: DESIGN.md)
+// one-wave workgroups of `bytes` of LDS cost no occupancy: eight still fit a CU, or all T tiles are resident at once anyway (few chains)
+static bool lds_resident(size_t bytes, int T, int cus)
 {
-    const size_t d4 = (size_t)((d + 3) & ~3), nt = (size_t)((d + 15) / 16);
-    // single pass: products and ss chains reuse the vector's rows
-    const size_t rows = (nt <= 4) ? std::max(d4, 4 * nt) : d4 + 16 * nt + 4 * nt;
-    return rows * 64 * sizeof(double);
+    const int per_cu = (int)(LDS_PER_CU / bytes);
+    return per_cu >= 8 || (per_cu >= 1 && (long long)T <= (long long)per_cu * cus);
 }
 static bool pooled_use_mfma(const mcmcx_engine *h, const mcx_switches &sw)
 {
@@ -28,7 +26,7 @@ static bool pooled_use_mfma(const mcmcx_engine *h, const mcx_switches &sw)
         if (h->d < dmin) return false;
     }
     if (sw.pooled_scalar > 0) return false;                                            // A/B switch for tests: the lane-per-chain kernel
-    return pooled_mfma_lds(h->d) <= 160 * 1024;
+    return PooledMfmaLds(h->d).bytes <= LDS_PER_CU;
 }
 // iteration cut at the evaluations
 static bool phased(const mcmcx_engine *h) { return h->tkind == TGT_HOST || h->tkind == TGT_EXPCOLS || h->tkind == TGT_MODULE; }
@@ -40,9 +38,9 @@ static int kernel_method(const mcmcx_engine *h)
     const int m = h->cfg.method;
     return (m == MCMCX_METHOD_RAM && !h->pooled) ? M_RAM : (m == MCMCX_METHOD_ER ? M_ER : M_DRAM);
 }
-static size_t lds_bytes(const mcmcx_engine *h) { return (size_t)h->d * 64 * sizeof(double) * 2; }   // adapt / DR work vectors
-static bool dr_fits_lds(const mcmcx_engine *h) { return lds_bytes(h) <= 160 * 1024; }          // npar <= 160
-static size_t lds_step(const mcmcx_engine *h) { return h->plan.dr_lds ? lds_bytes(h) : 0; }
+static bool dr_fits_lds(const mcmcx_engine *h) { return DrLds::bytes(h->d) <= LDS_PER_CU; }    // npar <= 160
+// the phase kernels, step_kernel_cols and run1_kernel: delayed rejection's two work vectors where they are in LDS (EngineDev::dr_lds)
+static size_t lds_step(const mcmcx_engine *h) { return DrLds::bytes(h->d, h->plan.dr_lds); }
 // step_kernel_dr keeps the second stage's two vectors in LDS, step_kernel_dr_big in global scratch.  LDS pays while eight waves
 // still fit a CU (npar <= 20: 6.9e8 against 6.0e8 iterations/s at 20); beyond, the waves it costs are worth more than the bytes
 // it saves (npar 24: 3.1e8 against 4.1e8, 64: 3.2e7 / 4.6e7, 100: 0.8e7 / 1.7e7 -- tools/dr_sweep.py)
@@ -52,7 +50,7 @@ static bool dr_vectors_in_lds(const mcmcx_engine *h, const mcx_switches &sw, int
 {
     if (!dr_fits_lds(h)) return false;
     if (sw.dr_big >= 0) return sw.dr_big == 0;                                        // A/B switch for tests: 1 = global scratch, 0 = LDS
-    return lds_bytes(h) * (size_t)min_waves <= 160 * 1024;
+    return DrLds::bytes(h->d) * (size_t)min_waves <= LDS_PER_CU;
 }
 static void launch_init(mcmcx_engine *h)
 { hipLaunchKernelGGL(init_kernel, dim3(h->ntiles), dim3(64), 0, h->stream, h->E); }
@@ -231,7 +229,7 @@ static bool pooled_two_waves(const mcmcx_engine *h, const mcx_switches &sw)
 {
     // (test switch: either instance on a small problem)
     if (sw.pooled_waves == 1 || sw.pooled_waves == 2) return sw.pooled_waves == 2;
-    return h->ntiles >= (pooled_mfma_lds(h->d) * 8 <= 160 * 1024 ? 2048 : 8192);
+    return h->ntiles >= (PooledMfmaLds(h->d).bytes * 8 <= LDS_PER_CU ? 2048 : 8192);
 }
 // pooled_mfma_ks_kernel: the forty-row LDS vector (eight tiles on a CU whatever npar is) where the whole vector leaves fewer, for the
 // problems that fill those CUs: npar 41..64, no delayed rejection, and two tiles per SIMD or more.  Against pooled_mfma_kernel<false, true>
@@ -251,6 +249,8 @@ static bool pooled_forty_rows(const mcmcx_engine *h, const mcx_switches &sw)
 #define STEP_RS (h->d_ramscale + it0)
 #define STEP_TGT h->E.tgt.mu, h->E.tgt.lamT
 #define G1 dim3(h->ntiles), dim3(64)
+// a step form's launch (mcx_step.hpp): the form names its kernel and its LDS
+#define STEP_LAUNCH(Form, ...) hipLaunchKernelGGL((step_entry(Form())), G1, StepLds<Form>::bytes(h->d, h->P), STEP_ARGS, __VA_ARGS__)
 // method = 'ram' with few chains: sixteen lanes per chain, the factor in registers, dchud / dchdd on it there (mcx_group_ram.hpp) where it
 // is the faster one (tools/ram_group_sweep.py, profiles/r05_b/ram_group_sweep.txt: chain-iterations/s of both families over npar, chain
 // count and regime): one wave per SIMD and four chains per wave, so the chip holds 4096 chains at once and the kernel saturates there
@@ -305,62 +305,54 @@ static const KernelEntry STEP_TABLE[] = {
          (const double *)h->pool.d_iC); }, SH_R | SH_DR},
     // ---- pooled mode (one shared factor)
     {"step", "pooled_mfma_kernel<true>", [](const mcmcx_engine *h) { return h->plan.pooled_dr_mfma; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<true>, G1, pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT,
-         h->pool.d_RT, h->pool.d_R2T, h->pool.d_iCd); }, SH_RT | SH_DRT},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<true>, G1, PooledMfmaLds(h->d).bytes, STEP_ARGS,
+         STEP_TGT, h->pool.d_RT, h->pool.d_R2T, h->pool.d_iCd); }, SH_RT | SH_DRT},
     MCX_VARIANT_STEP_ENTRIES
     {"step", "pooled_mfma_ks_kernel", [](const mcmcx_engine *h) { return h->plan.pooled_forty_rows; },
      [](mcmcx_engine *h, int it0, int it1) {
          // (npar 49..52: the fourth output block has four rows and goes through the 4 x 4 x 4 instruction)
-         const size_t lds = (size_t)PKS * 64 * sizeof(double);
+         const size_t lds = pooled_ks_lds();
          if (((h->d + 3) & ~3) == 52) hipLaunchKernelGGL(pooled_mfma_ks_kernel<true>, G1, lds, STEP_ARGS, STEP_TGT, h->pool.d_RT);
          else hipLaunchKernelGGL(pooled_mfma_ks_kernel<false>, G1, lds, STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT},
     {"step", "pooled_mfma_kernel<false, true>", [](const mcmcx_engine *h) {
         return h->plan.pooled_mfma && h->plan.pooled_two_waves; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((pooled_mfma_kernel<false, true>), G1, pooled_mfma_lds(h->d), STEP_ARGS,
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((pooled_mfma_kernel<false, true>), G1, PooledMfmaLds(h->d).bytes, STEP_ARGS,
          STEP_TGT, h->pool.d_RT, (const double *)nullptr, (const double *)nullptr); }, SH_RT},
     {"step", "pooled_mfma_kernel<false>", [](const mcmcx_engine *h) { return h->plan.pooled_mfma; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<false>, G1, pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT,
-         h->pool.d_RT, (const double *)nullptr, (const double *)nullptr); }, SH_RT},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma_kernel<false>, G1, PooledMfmaLds(h->d).bytes, STEP_ARGS,
+         STEP_TGT, h->pool.d_RT, (const double *)nullptr, (const double *)nullptr); }, SH_RT},
     {"step", "step_kernel_pooled_dr_big", [](const mcmcx_engine *h) { return h->pooled && h->dodr && !h->plan.dr_vectors_in_lds; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_pooled_dr_big, G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR, h->pool.d_R2, h->pool.d_iC); }, SH_R | SH_DR},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepPooledDrBig, STEP_RS, STEP_TGT, h->E.sharedR, h->pool.d_R2, h->pool.d_iC); },
+     SH_R | SH_DR},
     {"step", "step_kernel_pooled_dr", [](const mcmcx_engine *h) { return h->pooled && h->dodr; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_pooled_dr, G1, lds_step(h), STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR, h->pool.d_R2, h->pool.d_iC); }, SH_R | SH_DR},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepPooledDr, STEP_RS, STEP_TGT, h->E.sharedR, h->pool.d_R2, h->pool.d_iC); },
+     SH_R | SH_DR},
     {"step", "step_kernel<false, false, true>", [](const mcmcx_engine *h) { return h->pooled != 0; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<false, false, true>), G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR); }, SH_R},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepPooled, STEP_RS, STEP_TGT, h->E.sharedR); }, SH_R},
     // ---- method = 'ram', per-chain factors
     {"step", "group_ram_kernel", [](const mcmcx_engine *h) { return h->plan.ram_group_d4 != 0; }, launch_group_ram},
     {"step", "step_kernel_ram_fullr", [](const mcmcx_engine *h) { return kernel_method(h) == M_RAM && h->usesvd; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ram_fullr, G1, 0, STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR);
-         }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRamFullr, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel_ram_ldsr", [](const mcmcx_engine *h) {
         return kernel_method(h) == M_RAM && h->plan.lds_form == LDS_RAM_R; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ram_ldsr, G1, (size_t)(2 * h->d + h->P) * 64 * sizeof(double),
-         STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRamLdsr, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel_ram_wide", [](const mcmcx_engine *h) {
         return kernel_method(h) == M_RAM && h->d > RAM_SMALL_MAX && h->plan.ram_wide; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ram_wide, G1, (size_t)NLC * 2 * 64 * sizeof(double), STEP_ARGS,
-         STEP_RS, STEP_TGT, h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRamWide, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel<true, false, false>", [](const mcmcx_engine *h) { return kernel_method(h) == M_RAM; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<true, false, false>), G1,
-         (size_t)NLC * 2 * 64 * sizeof(double), STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRam, STEP_RS, STEP_TGT, h->E.sharedR); }},
     // ---- delayed rejection, per-chain factors: the second stage's two vectors in global scratch / in LDS
     {"step", "step_kernel_dr_big", [](const mcmcx_engine *h) { return h->dodr && !h->plan.dr_vectors_in_lds; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_dr_big, G1, 0, STEP_ARGS, STEP_TGT); }},
     {"step", "step_kernel_dr", [](const mcmcx_engine *h) { return h->dodr != 0; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_dr, G1, lds_step(h), STEP_ARGS, STEP_TGT); }},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_dr, G1, DrLds::bytes(h->d), STEP_ARGS, STEP_TGT); }},
     // ---- AM / Metropolis / early rejection: state + factor in LDS, state in LDS, nothing in LDS
     {"step", "step_kernel_ldsr", [](const mcmcx_engine *h) { return h->plan.lds_form == LDS_STATE_R; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ldsr, G1, (size_t)(2 * h->d + h->P) * 64 * sizeof(double),
-         STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepLdsr, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel_ldsv", [](const mcmcx_engine *h) { return h->plan.lds_form != LDS_NONE; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_ldsv, G1, (size_t)4 * h->d * 64 * sizeof(double), STEP_ARGS,
-         STEP_RS, STEP_TGT, h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepLdsv, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel<false, false, false>", [](const mcmcx_engine *) { return true; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<false, false, false>), G1, 0, STEP_ARGS, STEP_RS, STEP_TGT,
-         h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepPlain, STEP_RS, STEP_TGT, h->E.sharedR); }},
 };
 static void launch_step(mcmcx_engine *h, int it0, int it1)
 {
@@ -385,9 +377,6 @@ static int dev_bcast(mcmcx_engine *h, double *dst, const std::vector<double> &v)
 }
 // the dense layout's length (PooledState): d4 rows (pad rows zero) + slack; the stride of pooled SCAM's U block
 static size_t dense_len(const mcmcx_engine *h) { return (size_t)((h->d + 3) & ~3) * h->d + PWS; }
-// X [16 nt][64], Q [4 nt][64], zb, fl, mu [16 nt]
-static size_t scam_pooled_lds(int d) {
-    return ((size_t)((d + 15) / 16) * (16 + 4) * 64 + 128 + (size_t)((d + 15) / 16) * 16) * sizeof(double); }
 // 13..15 output blocks (npar 193..240): twelve waves of 170 registers (scam_pooled12_kernel) instead of sixteen of 128
 static bool scam_use_12(const mcmcx_engine *h, const mcx_switches &sw)
 {
@@ -399,13 +388,12 @@ static bool scam_use_12(const mcmcx_engine *h, const mcx_switches &sw)
 // rotation column (g_U = nullptr) -- the target's d x d product on the matrix cores instead of lane by lane
 static bool scam_fast_tile_kernel(const mcmcx_engine *h, const mcx_switches &sw)
 {
-    return h->cfg.scam_fast && h->tkind == TGT_GAUSS && !h->has_lo && !h->has_hi && !h->has_pri && scam_pooled_lds(h->d) <= 160 * 1024 &&
-           !(sw.scam_fast_lanes > 0);
+    return h->cfg.scam_fast && h->tkind == TGT_GAUSS && !h->has_lo && !h->has_hi && !h->has_pri &&
+           ScamPooledLds(h->d).bytes <= LDS_PER_CU && !(sw.scam_fast_lanes > 0);
 }
 // few tiles: several waves per tile (scam_mw_kernel), so that a sub-step is not bound by the latency of one wave's loads
 // while most of the chip idles -- as many waves as keep the chip's ~2048 resident-wave slots busy, at most 8 (sixteen
 // waves of 128 registers spill the products' panels)
-static size_t scam_mw_lds(const mcmcx_engine *h) { return (size_t)(4 * ((h->d + 15) / 16) + 2) * 64 * sizeof(double); }
 static int scam_tile_waves(const mcmcx_engine *h, const mcx_switches &sw)
 {
     int nw = 1;
@@ -413,10 +401,10 @@ static int scam_tile_waves(const mcmcx_engine *h, const mcx_switches &sw)
     while (nw < 8 && (long long)h->ntiles * nw * 2 <= 8192) nw *= 2;
     { const int v = sw.scam_waves; if (v == 1 || v == 2 || v == 4 || v == 8) nw = v; }   // A/B switch for tests
     // (npar > 1200: the one-wave kernel needs no LDS)
-    if (scam_mw_lds(h) > 160 * 1024) nw = 1;
+    if (ScamMwLds(h->d).bytes > LDS_PER_CU) nw = 1;
     return nw;
 }
-#define SCAM_POOLED_ARGS scam_pooled_lds(h->d), h->stream, h->E, it0, it1, h->E.tgt.mu, h->E.tgt.lamT
+#define SCAM_POOLED_ARGS ScamPooledLds(h->d).bytes, h->stream, h->E, it0, it1, h->E.tgt.mu, h->E.tgt.lamT
 // (SH_UREP: the per-chain kernels read every chain's own rotation, E.Rf / E.qstd -- in pooled mode above npar 240, copies of the one)
 static const KernelEntry SCAM_TABLE[] = {
     {"scam", "step_kernel_cols<scam>", [](const mcmcx_engine *h) { return h->plan.fused_cols && !h->pooled; },
@@ -438,14 +426,14 @@ static const KernelEntry SCAM_TABLE[] = {
         hipLaunchKernelGGL(scam_pooled_kernel, dim3(h->ntiles), dim3(64 * nw), SCAM_POOLED_ARGS, (const double *)nullptr,
             (const double *)nullptr, (const double *)nullptr); }, SH_UREP},
     {"scam", "scam_mw_kernel<8>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 8; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<8>, dim3(h->ntiles), dim3(512), scam_mw_lds(h), STEP_ARGS,
-         STEP_TGT); }, SH_UREP},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<8>, dim3(h->ntiles), dim3(512), ScamMwLds(h->d).bytes,
+         STEP_ARGS, STEP_TGT); }, SH_UREP},
     {"scam", "scam_mw_kernel<4>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 4; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<4>, dim3(h->ntiles), dim3(256), scam_mw_lds(h), STEP_ARGS,
-         STEP_TGT); }, SH_UREP},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<4>, dim3(h->ntiles), dim3(256), ScamMwLds(h->d).bytes,
+         STEP_ARGS, STEP_TGT); }, SH_UREP},
     {"scam", "scam_mw_kernel<2>", [](const mcmcx_engine *h) { return h->plan.scam_waves == 2; },
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<2>, dim3(h->ntiles), dim3(128), scam_mw_lds(h), STEP_ARGS,
-         STEP_TGT); }, SH_UREP},
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_mw_kernel<2>, dim3(h->ntiles), dim3(128), ScamMwLds(h->d).bytes,
+         STEP_ARGS, STEP_TGT); }, SH_UREP},
     {"scam", "scam_kernel", [](const mcmcx_engine *) { return true; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(scam_kernel, G1, 0, STEP_ARGS, STEP_TGT); }, SH_UREP},
 };
@@ -492,18 +480,18 @@ static SvdPlan plan_svd(int d, int nlanes)
         const int RL = d <= 64 ? 8 : d <= 128 ? 16 : 25;
         a.sweep_name = RL == 8 ? MCX_SVD_FORM(sweep32, svd_sweep_stream32_kernel<8>)
             : RL == 16 ? MCX_SVD_FORM(sweep32, svd_sweep_stream32_kernel<16>) : MCX_SVD_FORM(sweep32, svd_sweep_stream32_kernel<25>);
-        a.sweep_lds = (size_t)33 * (8 * RL + 2) * sizeof(double);
+        a.sweep_lds = svd_ring_lds(svd_ring_cols(32, false), svd_ring_ls(RL));
     } else {
         const int RL = d <= 208 ? 26 : 32;
         a.svd_sb = 24;                               // pair-lanes: whole waves of octets, one wave of loaders at least
         a.sweep_name = RL == 26 ? MCX_SVD_FORM(sweep, svd_sweep_stream_kernel<26>) : MCX_SVD_FORM(sweep, svd_sweep_stream_kernel<32>);
-        a.sweep_lds = (size_t)(a.svd_sb + 2) * (8 * RL + 2) * sizeof(double);
+        a.sweep_lds = svd_ring_lds(svd_ring_cols(a.svd_sb, true), svd_ring_ls(RL));
     }
     const int RP = d <= 64 ? 4 : d <= 128 ? 8 : d <= 208 ? 13 : 16;
     a.applyv_name = RP == 4 ? MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<4>)
         : RP == 8 ? MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<8>)
         : RP == 13 ? MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<13>) : MCX_SVD_FORM(applyv, svd_applyv_stream32_kernel<16>);
-    a.applyv_lds = (size_t)33 * (4 * RP + 6) * sizeof(double);
+    a.applyv_lds = svd_ring_lds(svd_ring_cols(32, false), svd_ring_slot(RP));
     a.applyv_grid = (unsigned)(32 * ((nlanes + 7) / 8));                  // four one-wave workgroups per chain, a chain's on one XCD
     return a;
 }
@@ -515,9 +503,8 @@ static void plan_adapt(const mcmcx_engine *h, KernelPlan &p)
     const int d = h->d;
     a.n10 = (d + TD - 1) / TD; a.noff = a.n10 * (a.n10 - 1) / 2;          // blocks of ten (triangular on the diagonal)
     a.g8 = (unsigned)(8 * ((h->ntiles + 7) / 8));
-    // one d-vector / the Cholesky's diagonal block (18 kB: eight waves per CU up to npar 36)
-    a.post_lds = std::max(lds_bytes(h) / 2, (size_t)36 * 64 * sizeof(double));
-    const bool xg = a.post_lds > 160 * 1024;
+    a.post_lds = adapt_post_lds(d);
+    const bool xg = a.post_lds > LDS_PER_CU;
     if (xg) a.post_lds = 0;
     a.post = h->usesvd ? (xg ? adapt_post_kernel<true, true> : adapt_post_kernel<true, false>)
                        : (xg ? adapt_post_kernel<false, true> : adapt_post_kernel<false, false>);
@@ -530,7 +517,7 @@ static void plan_adapt(const mcmcx_engine *h, KernelPlan &p)
         a.factor_name = nc == 1 ? "tile_factor_kernel<1,4>" : nc == 2 ? "tile_factor_kernel<2,4>" : nc == 3 ? "tile_factor_kernel<3,2>"
             : "tile_factor_kernel<4,1>";
         a.factor_block = (unsigned)(64 * nw);
-        a.factor_lds = (size_t)ch * (h->P | 1) * sizeof(double) + (size_t)ch * sizeof(int);
+        a.factor_lds = TileFactorLds(h->P, nw).bytes;
         a.factor_grid = a.g8 * (unsigned)(64 / ch);
     }
     if (p.svd_blocked) a.svd = plan_svd(d, h->nlanes);
@@ -559,25 +546,22 @@ static void plan_kernels(mcmcx_engine *h)
     p.dr_vectors_in_lds = dr_vectors_in_lds(h, sw, h->pooled ? 4 : 8);
     {   // plain AM / Metropolis / ER step kernel: state and scratch vectors in LDS (4 d x 512 bytes per wave) when that costs no
         // occupancy -- eight waves per CU still fit (npar <= 10), or all tiles are resident at once anyway (few chains)
-        const size_t per_wave = (size_t)4 * d * 64 * sizeof(double);
-        const int per_cu = (int)((size_t)160 * 1024 / per_wave);
         hipDeviceProp_t prop;
         int cus = 256;
         if (hipGetDeviceProperties(&prop, c.device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        const bool fits = per_cu >= 8 || (per_cu >= 1 && (long long)T <= (long long)per_cu * cus);
+        const bool fits = lds_resident(StepLds<StepLdsv>::bytes(d, P), T, cus);
         // (MCMCX_LDS_SCRATCH = 0: off, A/B)
         p.lds_form = (!h->pooled && !h->dodr && c.method != MCMCX_METHOD_RAM && c.method != MCMCX_METHOD_SCAM && fits
             && sw.lds_scratch != 0) ? LDS_STATE : LDS_NONE;
         // ... and the packed factor with it (step_kernel_ldsr) where one column panel covers npar and state + factor of all tiles
         // are resident at once: (2 npar + npar (npar + 1) / 2) x 512 bytes per wave, 38 KiB at npar = 10 = four waves per CU
-        const size_t per_wave_r = (size_t)(2 * d + P) * 64 * sizeof(double);
-        const int per_cu_r = (int)((size_t)160 * 1024 / per_wave_r);
-        const bool fits_r = per_cu_r >= 8 || (per_cu_r >= 1 && (long long)T <= (long long)per_cu_r * cus);
+        const bool fits_r = lds_resident(StepLds<StepLdsr>::bytes(d, P), T, cus);
         // MCMCX_LDS_SCRATCH=1: the state only (A/B)
         if (p.lds_form != LDS_NONE && !h->usesvd && d <= TW && fits_r && sw.lds_scratch != 1) p.lds_form = LDS_STATE_R;
         // method='ram' (per-chain factor, Cholesky form): the factor DCHUD / DCHDD rewrite every iteration, and their rotations, in LDS for
         // the launch where one column panel covers npar and all tiles are resident at once (step_kernel_ram_ldsr)
-        if (!h->pooled && c.method == MCMCX_METHOD_RAM && !h->usesvd && d <= RW && fits_r && sw.lds_scratch != 0) p.lds_form = LDS_RAM_R;
+        if (!h->pooled && c.method == MCMCX_METHOD_RAM && !h->usesvd && d <= RW && lds_resident(StepLds<StepRamLdsr>::bytes(d, P), T, cus)
+            && sw.lds_scratch != 0) p.lds_form = LDS_RAM_R;
     }
     // the user's functions on the host and at most sixteen tiles: candidate, results and flags in mapped host memory -- a phase kernel's
     // stores ARE the hand-over, the host's results are read by the next one in place (MCMCX_HOST_MAPPED=0: device buffers and copies)
@@ -587,7 +571,7 @@ static void plan_kernels(mcmcx_engine *h)
     // (MCMCX_HOST_FUSE=0: one launch per phase, the A/B form the tests compare with)
     p.host_fuse = sw.host_fuse != 0;
     // pooled SCAM: npar > 240: slower, not refused -- scam_kernel / scam_mw_kernel on per-chain copies; a user target: the per-chain phases
-    p.scam_replicated = h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM && (scam_pooled_lds(d) > 160 * 1024 || pphase);
+    p.scam_replicated = h->usesvd && h->pooled && c.method == MCMCX_METHOD_SCAM && (ScamPooledLds(d).bytes > LDS_PER_CU || pphase);
     p.pooled_mfma = pooled_use_mfma(h, sw) && !pphase;
     p.pooled_dr_mfma = p.pooled_mfma && h->dodr;                 // the second stage on the matrix cores too
     p.pooled_two_waves = pooled_two_waves(h, sw);

@@ -47,7 +47,7 @@ static int quant_select_launch(const QuantWin &A, unsigned long long *w, int nr,
     const long long t4 = ((long long)T + 3) / 4;
     const long long gx = std::min(t4, std::max<long long>(std::max(1, 2560 / nf), (t4 + 127) / 128));
     const dim3 grid((unsigned)gx, (unsigned)nf, (unsigned)((A.win.ns + A.chunk - 1) / A.chunk)), block(256);
-    const size_t lds = (size_t)nr * QUANT_NB * sizeof(unsigned int);
+    const size_t lds = quant_hist_lds(nr);
     hipLaunchKernelGGL(quant_init_kernel, dim3((unsigned)((m * QUANT_NB + 255) / 256)), block, 0, stream, S, R, nf);
     for (int sh = 64 - QUANT_B; sh >= 0; sh -= QUANT_B) {
         hipLaunchKernelGGL(quant_hist_kernel, grid, block, lds, stream, A, S, sh);

@@ -43,6 +43,14 @@ MCX_DEV double tree64(F &&val)
 // x value formed from global memory where it is used -- the same operations on the same operands, so the same bits; only the four
 // 64-vectors (count, alpha or stayed, sign, sum(u**2)) and the chains' a = rs (alpha - alphatarget) stay in LDS.  Slower (each term reads
 // its 2 x 64 values through L2); any npar.
+// Its LDS, in doubles: x [64][DP] the tile's vectors, chain-major with the odd stride DP = d | 1 (BIG: none) | count [64] | alpha or stayed
+// [64] | sign(a) [64] | sum(u**2) [64] | a [64] (BIG)
+struct MomentsLds {
+    int DP;
+    size_t sp0, sp1, sg, ssu, sa, bytes;                            // (x at 0)
+    MCX_HD MomentsLds(int d, bool big) : DP(big ? 0 : (d | 1)), sp0((size_t)64 * DP), sp1(sp0 + 64), sg(sp1 + 64), ssu(sg + 64),
+        sa(ssu + 64), bytes((sa + 64) * sizeof(double)) {}
+};
 template <bool BIG>
 __global__ __launch_bounds__(256) void moments_kernel(EngineDev E, double *out, int nchains, int kind, int it, double rs)
 {
@@ -51,9 +59,11 @@ __global__ __launch_bounds__(256) void moments_kernel(EngineDev E, double *out, 
     // v_l + v_{l^1}, (..) + (..)_{l^2}, ... a xor-butterfly leaves in lane 0 -- as they come (tree64).  No barrier after the first, every
     // lane on a term of its own; the old form (one chain per lane, 64 terms at a time transposed through LDS) spent its time
     // in the latencies of 1300 global loads and 2 x 20 barriers per tile at four waves per CU.
-    extern __shared__ double XS[];                      // x[64][DP]; then count[64], alpha or stayed [64], sign(a) [64], sum(u**2) [64]
-    const int tid = threadIdx.x, tile = blockIdx.x, d = E.d, P = E.P, DP = BIG ? 0 : (d | 1);
-    double *sp0 = XS + (size_t)64 * DP, *sp1 = sp0 + 64, *sg = sp1 + 64, *ssu = sg + 64, *sa = ssu + 64;
+    extern __shared__ double XS[];
+    const int tid = threadIdx.x, tile = blockIdx.x, d = E.d, P = E.P;
+    const MomentsLds lds(d, BIG);
+    const int DP = lds.DP;
+    double *sp0 = XS + lds.sp0, *sp1 = XS + lds.sp1, *sg = XS + lds.sg, *ssu = XS + lds.ssu, *sa = XS + lds.sa;
     const double *theta_t = E.theta + (size_t)tile * d * 64;
     const double *z_t = E.zs + ((size_t)tile * 2 + (it & 1)) * d * 64;        // kind 2: the normals iteration `it` proposed with
     const int len = (kind == 2) ? 2 + P : (1 + d + P + (kind == 1 ? 1 : 0));

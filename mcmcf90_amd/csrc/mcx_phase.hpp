@@ -136,7 +136,7 @@ MCX_DEV void host_phase_body(const EngineDev &E, int tile, int lane, int it, con
     const int ny = E.ny;
     double *hev = E.hev + (size_t)tile * (NHE - 1 + ny) * 64;    // inbounds, prior, ss per column
     double *hx = E.hx + (size_t)tile * NHX * 64;
-    double *Y = X + (size_t)d * 64;
+    double *Y = X + (size_t)d * 64;                            // (DrLds, mcx_step.hpp)
     double *ssv = ny > 1 ? E.ssv + (size_t)tile * ny * 64 : nullptr, *s2v = ny > 1 ? E.s2v + (size_t)tile * ny * 64 : nullptr;
     double *ss2v = ny > 1 ? E.ss2v + (size_t)tile * ny * 64 : nullptr;
     const double *sshev = hev + (size_t)HE_SS * 64;              // the host's ss columns of the point just evaluated
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(64) void run1_kernel(EngineDev E, double *r1, int d
     double *sc = ssn + (size_t)ny * 64;
     const double *s2v = ny > 1 ? E.s2v + (size_t)tile * ny * 64 : nullptr;
     double *zs_t = E.zs + (size_t)tile * 2 * d * 64;
-    double *Y = X + (size_t)d * 64;
+    double *Y = X + (size_t)d * 64;                            // (DrLds, mcx_step.hpp)
     LaneState L;
     lane_load(E, tile, lane, L);
     if (MODE == 0) {

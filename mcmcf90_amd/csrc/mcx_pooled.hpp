@@ -68,12 +68,27 @@ MCX_DEV void mfma_wave_product(const double *__restrict__ M, const double *X, in
 // DR: delayed rejection's second stage on the same cores (drscale > 0): the stage-2 proposal with the shared R2 = R / drscale (g_R2T, dense
 // like g_RT), the target once more, and the two quadratic forms dx' iC dx of MCMC_DR_alpha13 as y = iC dx products against the dense
 // symmetric table g_iCd, each followed by the chain q = sum_i y_i dx_i ascending in i (lane = chain: y comes back through the LDS vector,
-// dx waits in the chain's global scratch EngineDev::xscr).  Operation for operation step_body<false, true, true> (the lane-per-chain form
+// dx waits in the chain's global scratch EngineDev::xscr).  Operation for operation step_body<StepPooledDr> (the lane-per-chain form
 // with the tables through the scalar cache), whose chains these are. W2 (without delayed rejection): 256 registers, so that two waves share
 // a SIMD (the LDS vector lets six waves on a CU at npar 50: two SIMDs with two).  The compiler spills ~40 doubles of state around the
 // products to fit, and with more tiles than SIMDs it is still faster (round 4; round 2's attempt predates the single-pass LDS layout): 97.1
 // -> 93.2 ms per 100 iterations of 1 048 576 chains at npar 50.  With one tile per SIMD or fewer there is nobody to share with and the
 // spills are all it buys (npar 20, 65536 chains: 2.1e9 against 2.6e9 proposals/s): the host takes the 512-register instance there.
+// Its LDS, rows of 64 doubles: X [d4] the tile's vector | T [16 nt] the products in (row, chain) order | Q [4 nt] the partial ss chains.
+// A single pass (nt <= 4) ALIASES the three on purpose, T = Q = X: the products (rows < d4 only) overwrite the vector they came from, and
+// the partial ss chains go over its first 4 nt rows once y = Lam v is in registers -- 512 d4 bytes of LDS per wave (26 KiB at d = 50: six
+// waves per CU)
+struct PooledMfmaLds {
+    size_t T, Q, bytes;                                            // (X at 0; offsets in doubles)
+    MCX_HD explicit PooledMfmaLds(int d)
+    {
+        const int d4 = (d + 3) & ~3, nt = (d + 15) >> 4;
+        const bool single = (nt <= 4);
+        T = single ? 0 : (size_t)d4 * 64;
+        Q = single ? 0 : T + (size_t)nt * 16 * 64;
+        bytes = (size_t)(single ? (d4 > 4 * nt ? d4 : 4 * nt) : d4 + 16 * nt + 4 * nt) * 64 * sizeof(double);
+    }
+};
 template <bool DR, bool W2 = false>
 __global__ __launch_bounds__(64, (!DR && W2) ? 2 : 1) void pooled_mfma_kernel(EngineDev E, int it0, int it1,
                                                          const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
@@ -84,10 +99,9 @@ __global__ __launch_bounds__(64, (!DR && W2) ? 2 : 1) void pooled_mfma_kernel(En
     const int lane = threadIdx.x, tile = blockIdx.x, d = E.d;
     const int d4 = (d + 3) & ~3, nt = (d + 15) >> 4, li = lane & 15, lk = lane >> 4;
     const bool single = (nt <= 4);                                  // one pass: the outputs may overwrite the input vector
-    // single pass: the products (rows < d4 only) overwrite the vector they came from, and the partial ss chains go over
-    // its first 4 nt rows once y = Lam v is in registers -- 512 d4 bytes of LDS per wave (26 KiB at d = 50: six waves per CU)
-    double *T = single ? X : X + (size_t)d4 * 64;                  // [16 nt][64] products in (row, chain) order
-    double *Q = single ? X : T + (size_t)nt * 16 * 64;             // [4 nt][64] partial ss chains
+    // PooledMfmaLds, spelled out (taking the offsets from it moves this kernel's instructions)
+    double *T = single ? X : X + (size_t)d4 * 64;
+    double *Q = single ? X : T + (size_t)nt * 16 * 64;
     double *theta_t = E.theta + (size_t)tile * d * 64;
     double *cand_t = E.cand + (size_t)tile * d * 64;
     double *c2_t = E.cs + (size_t)tile * 2 * d * 64;               // DR: the second-stage candidate

@@ -91,11 +91,12 @@ MCX_DEV void mfma_wave_part(const double *__restrict__ M, const double *X, int x
     }
 }
 
+MCX_HD size_t pooled_ks_lds() { return (size_t)PKS * 64 * sizeof(double); }     // X [PKS][64], whatever npar is
 template <bool S3>
 __global__ __launch_bounds__(64, 2) void pooled_mfma_ks_kernel(EngineDev E, int it0, int it1, const double *__restrict__ g_mu,
                                                                 const double *__restrict__ g_lamT, const double *__restrict__ g_RT)
 {
-    extern __shared__ double X[];                                   // [PKS][64]
+    extern __shared__ double X[];                                   // pooled_ks_lds()
     const int lane = threadIdx.x, tile = blockIdx.x, d = E.d;
     const int d4 = (d + 3) & ~3, nt = (d + 15) >> 4, li = lane & 15, lk = lane >> 4;      // 40 < d4 <= 64: nt = 3 or 4
     double *theta_t = E.theta + (size_t)tile * d * 64;

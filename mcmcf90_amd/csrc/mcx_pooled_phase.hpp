@@ -89,6 +89,13 @@ MCX_DEV void pooled_phase_propose(const EngineDev &E, int tile, int lane, double
 // proposal (delayed rejection).  The phases hand over through the chain's own state as in host_phase_seq_kernel; the decision of phase 2
 // reads the packed inverse covariance siC (quadform_sym_shared) and takes its two work vectors from the LDS the proposal uses after it.
 // Two waves per SIMD: what the LDS vector leaves a CU at npar 50 (six waves) needs no more.
+// Its LDS: the proposal's vector X [d4][64] doubles; phase 2's decision, which runs before it, takes its two work vectors (DrLds, where
+// they are in LDS) from the same rows
+MCX_HD size_t pooled_phase_mfma_lds(int d, bool dr_vectors)
+{
+    const size_t x = (size_t)((d + 3) & ~3) * 64 * sizeof(double), q = DrLds::bytes(d, dr_vectors);
+    return x > q ? x : q;
+}
 template <int PA, bool STAGE2>
 __global__ __launch_bounds__(64, 2) void pooled_phase_mfma_kernel(EngineDev E, int itA, int itB, const double *__restrict__ ramscale,
     const double *__restrict__ g_M, const double *__restrict__ siC, int keepz)

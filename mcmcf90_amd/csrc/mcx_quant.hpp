@@ -56,6 +56,7 @@ __global__ __launch_bounds__(256) void quant_init_kernel(QuantState S, QuantRank
 // + 4 gx, ..; blockIdx.z takes window samples z chunk .. (z + 1) chunk - 1.  The leading digits are nearly the same for every value
 // of a field, so a digit that is the same in all matching lanes of a wave is ONE add of their number (a ballot against the first
 // matching lane's digit); only a wave whose digits differ falls back to an atomic per lane.
+MCX_HD size_t quant_hist_lds(int nr) { return (size_t)nr * QUANT_NB * sizeof(unsigned int); }    // [nr][2**B] counters
 __global__ __launch_bounds__(256) void quant_hist_kernel(QuantWin A, QuantState S, int sh)
 {
     extern __shared__ unsigned int quant_lds[];

@@ -136,7 +136,12 @@ __global__ __launch_bounds__(64, MCX_SCAM_WAVES) void scam_kernel(EngineDev E, i
 // blocks of 16 rows are independent up to the running sum of their q_k, so the waves share panels / blocks without
 // changing one operation; wave 0 owns the per-chain scalar state (stream, ss1, counters), draws, decides, and hands the
 // deviate and the accept flag to the others through LDS.  Vectors stay in the per-chain global scratch (the workgroup's
-// waves run on one CU and meet at workgroup barriers).  lds: [16 nblk][64] partial chains, [64] deviates, [64] flags.
+// waves run on one CU and meet at workgroup barriers).
+// Its LDS, in doubles: Q [4 nblk][64] partial chains | zl [64] deviates | fl [64] flags
+struct ScamMwLds {
+    size_t zl, fl, bytes;                                           // (Q at 0)
+    MCX_HD explicit ScamMwLds(int d) : zl((size_t)4 * ((d + 15) / 16) * 64), fl(zl + 64), bytes((fl + 64) * sizeof(double)) {}
+};
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void scam_mw_kernel(EngineDev E, int it0, int it1,
                                                           const double *__restrict__ g_mu, const double *__restrict__ g_lamT)
@@ -144,7 +149,8 @@ __global__ __launch_bounds__(64 * NW) void scam_mw_kernel(EngineDev E, int it0, 
     extern __shared__ double lds_mw[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tile = blockIdx.x, d = E.d;
     const int nblk = (d + 15) / 16;
-    double *Q = lds_mw, *zl = lds_mw + (size_t)4 * nblk * 64, *fl = zl + 64;
+    const ScamMwLds lds(d);
+    double *Q = lds_mw, *zl = lds_mw + lds.zl, *fl = lds_mw + lds.fl;
     double *theta_t = E.theta + (size_t)tile * d * 64;
     double *cand_t = E.cand + (size_t)tile * d * 64;
     double *rot_t = E.cs + (size_t)tile * 2 * d * 64;
@@ -315,6 +321,17 @@ MCX_DEV void mfma_slots(const double *__restrict__ M, const double *X, int lane,
 // offset o*64 + c in a tile-interleaved vector (and in X) is e0 + (BW ? 16 s : 1024 s) + 256 r.  X has 16*nt rows, so
 // every element has an LDS home; rows >= d are written as zeros (the k loop reads the rows < d4 only).
 // SC: the scalar wave (the last one).  A template parameter, so that the other fifteen waves carry
+// The LDS of scam_pooled_kernel / scam_pooled12_kernel, in doubles: X [16 nt][64] the products' vector | Q [4 nt][64] partial ss chains |
+// zb [64], fl [64] per chain: the deviate, the accept flag | mu [16 nt] the target's mean: read at every third fill
+struct ScamPooledLds {
+    size_t Q, zb, fl, mu, bytes;                                    // (X at 0)
+    MCX_HD explicit ScamPooledLds(int d)
+    {
+        const int nt = (d + 15) >> 4;
+        Q = (size_t)nt * 16 * 64; zb = Q + (size_t)nt * 4 * 64; fl = zb + 64; mu = fl + 64;
+        bytes = (mu + (size_t)nt * 16) * sizeof(double);
+    }
+};
 template <bool BW, int NS, bool SC, bool XS = false>
                                       // neither the generator nor the per-chain state: at 128 registers a wave they spilled around their
                                       // MFMAs XS (scam_pooled12_kernel): a block wave with a FIFTH slot, chain group xgrp of block xblk
@@ -324,9 +341,10 @@ MCX_DEV void scam_pooled_body(const EngineDev &E, int it0, int it1, double *X, i
                               int xblk = 0, int xgrp = 0)
 {
     const int tile = blockIdx.x, d = E.d, d4 = (d + 3) & ~3, nt = (d + 15) >> 4, li = lane & 15, lk = lane >> 4;
-    double *Q = X + (size_t)nt * 16 * 64;                                       // [4*nt][64] partial ss chains
-    double *zb = Q + (size_t)nt * 4 * 64, *fl = zb + 64;                      // per chain: the deviate, the accept flag
-    double *mul = fl + 64;                                                      // the target's mean, [16 nt]: read at every third fill
+    // ScamPooledLds, spelled out (taking the offsets from it moves these kernels' instructions)
+    double *Q = X + (size_t)nt * 16 * 64;
+    double *zb = Q + (size_t)nt * 4 * 64, *fl = zb + 64;
+    double *mul = fl + 64;
     constexpr bool sc = SC;                                                     // the scalar wave
     const bool gauss = (E.tgt.kind == TGT_GAUSS);
     const bool cand_global = !gauss || E.tgt.pmu || E.tgt.lo || E.tgt.hi;       // prior / bounds / other targets read theta' per chain

@@ -442,26 +442,77 @@ MCX_DEV double quadform_sym_shared(const double *__restrict__ Ss, int lane, int 
 
 // ---------------------------------------------------------------- the step kernel
 // Iterations it0..it1 (absolute simuind) of MCMC_run (MCMC_run.F90:41-107) or MCMC_run_ram
-// (MCMC_run_ram.F90:45-81) for one tile of 64 chains.  LDS is used only by the delayed-rejection
-// quadratic forms (2*d*64 doubles when dodr, none otherwise).
-template <bool RAM, bool DR, bool POOLED, bool WIDE_T = (RAM || (!DR && !POOLED)), bool FULLR = false, bool LDSV = false,
-    bool LDSR = false, bool XG = false, int RWT = RW>
+// (MCMC_run_ram.F90:45-81) for one tile of 64 chains, in the form F names.
+#ifndef MCX_AM_WAVES
+#define MCX_AM_WAVES 2
+#endif
+#ifndef MCX_AM_WIDE
+#define MCX_AM_WIDE true
+#endif
+// ---- the forms step_body is compiled in: the defaults, the form of step_kernel<RAM, DR, POOLED>, and one named form per further entry
+struct StepForm {
+    static constexpr bool RAM = false, DR = false, POOLED = false;
+    static constexpr bool WIDE_T = false;            // target_ss reads the candidate once (where registers allow)
+    static constexpr bool FULLR = false;             // RAM with condmax > 0: the full SVD factor (ram_update_full)
+    static constexpr bool LDSV = false;              // state, candidate and normals in LDS (a compile-time choice: ds_read / ds_write, not
+    static constexpr bool LDSR = false;              // flat); ... and the chain's packed factor too
+    static constexpr bool XG = false;                // DR: the quadratic forms' two vectors in the tile's global scratch (E.xscr), not LDS
+    static constexpr int RWT = RW;                   // ram_update's panel width
+};
+template <bool RAM_, bool DR_, bool POOLED_>
+struct StepFlags : StepForm {
+    static constexpr bool RAM = RAM_, DR = DR_, POOLED = POOLED_, WIDE_T = RAM_ || (!DR_ && !POOLED_ && MCX_AM_WIDE);
+};
+using StepPlain = StepFlags<false, false, false>;
+using StepRam = StepFlags<true, false, false>;
+using StepPooled = StepFlags<false, false, true>;
+struct StepLdsv : StepPlain { static constexpr bool LDSV = true; };
+struct StepLdsr : StepLdsv { static constexpr bool LDSR = true; };
+struct StepRamWide : StepRam { static constexpr int RWT = RW_WIDE; };
+struct StepRamLdsr : StepRam { static constexpr bool LDSR = true; };
+struct StepRamFullr : StepRam { static constexpr bool WIDE_T = false, FULLR = true; };
+struct StepPooledDr : StepFlags<false, true, true> {};
+struct StepPooledDrBig : StepPooledDr { static constexpr bool XG = true; };
+
+// ---- a form's dynamic LDS (one wave per workgroup), in rows of 64 doubles -- offsets in doubles, the launch's size in bytes:
+//   ldsv      theta [d] | cand [d] | zs [2 d]       the state, the proposal then candidate, this iteration's normals and the next one's
+//   ldsr      theta [d] | cand = zs [d] | R [P]     (npar <= TW) ONE vector serves as normals, proposal and candidate -- a single column
+//                                                   panel: the product has read every normal before it stores anything -- and the chain's
+//                                                   packed factor stays for the launch: AM only reads it between two ticks
+//   ram       rot [2 NLC]                           ram_update's rotations (c_k, s_k) of the first NLC rows (its lc)
+//   ram_ldsr  rot [2 d] | R [P]                     (npar <= RW: one column panel) every rotation, and behind them the factor that DCHUD /
+//                                                   DCHDD rewrite at every iteration -- north_star's "Cholesky factor staged in LDS"
+//   DR        X [d] | Y [d]                         the quadratic forms' two vectors (XG: the same two in global scratch, no LDS)
+//   otherwise (plain, pooled, ram_fullr) none
+template <class F>
+struct StepLds {
+    static constexpr bool ldsv = F::LDSV && !F::RAM && !F::DR && !F::POOLED, ldsr = ldsv && F::LDSR, ramr = F::RAM && F::LDSR && !F::FULLR;
+    static constexpr bool rot = F::RAM && !F::FULLR, xy = F::DR && !F::XG;
+    MCX_HD static size_t cand(int d) { return (size_t)d * 64; }
+    MCX_HD static size_t zs(int d) { return ldsr ? cand(d) : (size_t)2 * d * 64; }
+    MCX_HD static size_t R(int d) { return (size_t)2 * d * 64; }
+    MCX_HD static size_t Y(int d) { return (size_t)d * 64; }
+    MCX_HD static size_t bytes(int d, int P)
+    {
+        const size_t rows = (ldsr || ramr) ? (size_t)(2 * d + P) : ldsv ? (size_t)4 * d : rot ? (size_t)2 * NLC : xy ? (size_t)2 * d : 0;
+        return rows * 64 * sizeof(double);
+    }
+};
+
+template <class F>
 MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__restrict__ ramscale,
                        const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                        const double *__restrict__ g_sharedR, const double *__restrict__ g_sharedR2 = nullptr,
                        const double *__restrict__ g_sharediC = nullptr)
 {
+    constexpr bool RAM = F::RAM, DR = F::DR, POOLED = F::POOLED, WIDE_T = F::WIDE_T, FULLR = F::FULLR, XG = F::XG;
+    constexpr int RWT = F::RWT;
+    using L = StepLds<F>;
+    constexpr bool ldsv = L::ldsv, ldsr = L::ldsr, ramr = L::ramr;
     extern __shared__ double Xlds[];
     const int lane = threadIdx.x, tile = blockIdx.x, d = E.d;
-    // the delayed-rejection quadratic forms' two vectors: LDS, or (XG, a compile-time choice: no flat accesses) the chain's global scratch
     double *X = XG ? E.xscr + (size_t)tile * 2 * d * 64 : Xlds;
-    // step_kernel_ldsv: launched with 4 d x 512 bytes of LDS (a compile-time choice, so that the vectors' accesses are ds_read / ds_write,
-    // not flat)
-    constexpr bool ldsv = LDSV && !RAM && !DR && !POOLED;
-    // step_kernel_ldsr (npar <= TW): besides the state, the chain's packed factor stays in LDS for the launch -- AM only reads
-    // it between two ticks -- and ONE vector serves as normals, proposal and candidate (a single column panel: the product
-    // has read every normal before it stores anything)
-    constexpr bool ldsr = ldsv && LDSR;
+    // StepLds<F>'s offsets cand, zs, R and Y, spelled out (taking them from it moves instructions of the ldsv, ldsr, pooled_dr kernels)
     double *theta_g = E.theta + (size_t)tile * d * 64;
     double *theta_t = ldsv ? X : theta_g;
     double *cand_t = ldsv ? X + (size_t)d * 64 : E.cand + (size_t)tile * d * 64;           // proposal vector P, then candidate theta + P
@@ -469,9 +520,6 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
     double *zs_t = ldsr ? cand_t : (ldsv ? X + (size_t)2 * d * 64 : E.zs + (size_t)tile * 2 * d * 64);
     double *cs_t = E.cs + (size_t)tile * 2 * d * 64;           // RAM: rotations; DR: second-stage candidate
     if (ldsv) for (int k = 0; k < d; ++k) GV(theta_t, k) = GV(theta_g, k);
-    // step_kernel_ram_ldsr (npar <= RW: one column panel): the factor that DCHUD / DCHDD rewrite at every iteration stays in LDS for the
-    // launch, behind the 2 npar vectors of rotations -- north_star's "Cholesky factor staged in LDS" for the rank-one update itself
-    constexpr bool ramr = RAM && LDSR && !FULLR;
     double *Rt = (ldsr || ramr) ? X + (size_t)2 * d * 64 : E.R + (size_t)tile * E.P * 64;
     if (ldsr || ramr) { const double *Rg = E.R + (size_t)tile * E.P * 64; copy_vec(Rt, Rg, nullptr, lane, E.P); }
     double *Y = X + (size_t)d * 64;
@@ -694,6 +742,13 @@ MCX_DEV void quadform2_panels(const double *St, int lane, int d, const double *X
     }
 }
 
+// The second stage's two work vectors in LDS, X [d] | Y [d] rows of 64 doubles, of the kernels that do not take them from a step form:
+// dr_body<true> (normals, then dx_a | first-stage candidate, then dx_b) and, where EngineDev::dr_lds says the two fit a CU, the phase
+// kernels' and run1_kernel's quadratic forms (mcx_phase.hpp).  in_lds = false: none, the vectors are in global scratch
+struct DrLds {
+    MCX_HD static size_t Y(int d) { return (size_t)d * 64; }
+    MCX_HD static size_t bytes(int d, bool in_lds = true) { return in_lds ? (size_t)2 * d * 64 * sizeof(double) : 0; }
+};
 template <bool LDSV>      // the two vectors in LDS (a compile-time choice: a pointer that is LDS or global at run time means FLAT accesses)
 MCX_DEV void dr_body(const EngineDev &E, int it0, int it1, const double *__restrict__ g_mu, const double *__restrict__ g_lamT)
 {
@@ -701,7 +756,7 @@ MCX_DEV void dr_body(const EngineDev &E, int it0, int it1, const double *__restr
     const int lane = threadIdx.x, tile = blockIdx.x, d = E.d;
     double *theta_t = E.theta + (size_t)tile * d * 64;
     double *c2_t = E.cs + (size_t)tile * 2 * d * 64;           // second-stage candidate (global scratch)
-    // normals of the stage at hand, then dx_a = newpar2 - newpar  |  first-stage candidate, then dx_b = oldpar - newpar
+    // normals of the stage at hand, then dx_a = newpar2 - newpar  |  first-stage candidate, then dx_b = oldpar - newpar (DrLds: X | Y)
     double *zb_t = LDSV ? X : c2_t + (size_t)d * 64;
     double *cand_t = LDSV ? X + (size_t)d * 64 : E.cand + (size_t)tile * d * 64;
     double *ysa_t = E.zs + (size_t)tile * 2 * d * 64, *ysb_t = ysa_t + (size_t)d * 64;     // row chains between two panels of iC
@@ -808,41 +863,41 @@ __global__ __launch_bounds__(64, 2) void step_kernel_dr_big(EngineDev E, int it0
     const double *__restrict__ g_lamT)
 { dr_body<false>(E, it0, it1, g_mu, g_lamT); }
 
-#ifndef MCX_AM_WAVES
-#define MCX_AM_WAVES 2
-#endif
-#ifndef MCX_AM_WIDE
-#define MCX_AM_WIDE true
-#endif
+// ---- the entries: a kernel per form, and step_entry(form) naming it for the launch tables
 template <bool RAM, bool DR, bool POOLED>
 __global__ __launch_bounds__(64, RAM ? MCX_RAM_WAVES : (DR || POOLED) ? 2 : MCX_AM_WAVES) void step_kernel(EngineDev E, int it0, int it1,
     const double *__restrict__ ramscale,
                                                      const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                      const double *__restrict__ g_sharedR)
-{ step_body<RAM, DR, POOLED, (RAM || (!DR && !POOLED && MCX_AM_WIDE))>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+{ step_body<StepFlags<RAM, DR, POOLED>>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+template <bool RAM, bool DR, bool POOLED> inline auto step_entry(StepFlags<RAM, DR, POOLED>) { return step_kernel<RAM, DR, POOLED>; }
 // the plain AM / Metropolis / ER step with the state vector, the candidate and the two normal vectors in LDS (EngineDev::lds_scratch)
 __global__ __launch_bounds__(64, MCX_AM_WAVES) void step_kernel_ldsv(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
                                                      const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                      const double *__restrict__ g_sharedR)
-{ step_body<false, false, false, MCX_AM_WIDE, false, true>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+{ step_body<StepLdsv>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+inline auto step_entry(StepLdsv) { return step_kernel_ldsv; }
 // ... and the chain's packed factor too (npar <= TW; EngineDev::lds_scratch == 2): north_star's "Cholesky factor staged in LDS"
 __global__ __launch_bounds__(64, MCX_AM_WAVES) void step_kernel_ldsr(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
                                                      const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                      const double *__restrict__ g_sharedR)
-{ step_body<false, false, false, MCX_AM_WIDE, false, true, true>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+{ step_body<StepLdsr>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+inline auto step_entry(StepLdsr) { return step_kernel_ldsr; }
 
 // method='ram' at npar <= RW with few enough tiles: the factor in LDS for the launch (EngineDev::lds_scratch == 3)
 __global__ __launch_bounds__(64, 2) void step_kernel_ram_ldsr(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
                                                      const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                      const double *__restrict__ g_sharedR)
-{ step_body<true, false, false, true, false, false, true>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+{ step_body<StepRamLdsr>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+inline auto step_entry(StepRamLdsr) { return step_kernel_ram_ldsr; }
 
 // method='ram' above npar 20: step_kernel<true, false, false> with the wide column panels (RW_WIDE above)
 __global__ __launch_bounds__(64, MCX_RAM_WAVES) void step_kernel_ram_wide(EngineDev E, int it0, int it1,
     const double *__restrict__ ramscale,
                                                      const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                      const double *__restrict__ g_sharedR)
-{ step_body<true, false, false, true, false, false, false, false, RW_WIDE>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+{ step_body<StepRamWide>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+inline auto step_entry(StepRamWide) { return step_kernel_ram_wide; }
 
 // pooled mode with delayed rejection: the shared factor, its second-stage copy R2 = R / drscale and the shared inverse
 // covariance iC = dpotri(R) all come through the scalar cache (the host recomputes the three at every pooled tick)
@@ -850,7 +905,8 @@ __global__ __launch_bounds__(64, 2) void step_kernel_pooled_dr(EngineDev E, int 
                                                                const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                                const double *__restrict__ g_sharedR, const double *__restrict__ g_sharedR2,
                                                                const double *__restrict__ g_sharediC)
-{ step_body<false, true, true, false>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR, g_sharedR2, g_sharediC); }
+{ step_body<StepPooledDr>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR, g_sharedR2, g_sharediC); }
+inline auto step_entry(StepPooledDr) { return step_kernel_pooled_dr; }
 // ... with the two quadratic-form vectors in global scratch (EngineDev::xscr): above npar 20 the LDS form costs waves (51 KiB per wave
 // at npar 50: three waves per CU), and above 160 it does not fit at all
 __global__ __launch_bounds__(64, 2) void step_kernel_pooled_dr_big(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
@@ -858,13 +914,15 @@ __global__ __launch_bounds__(64, 2) void step_kernel_pooled_dr_big(EngineDev E, 
                                                                    const double *__restrict__ g_sharedR,
                                                                        const double *__restrict__ g_sharedR2,
                                                                    const double *__restrict__ g_sharediC)
-{ step_body<false, true, true, false, false, false, false, true>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR, g_sharedR2, g_sharediC); }
+{ step_body<StepPooledDrBig>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR, g_sharedR2, g_sharediC); }
+inline auto step_entry(StepPooledDrBig) { return step_kernel_pooled_dr_big; }
 
 // method='ram' with condmax > 0: the factor is the full SVD one (E.Rf), proposals are matmulx(R,u), the rank-one
 // adaptation runs on its upper triangle (ram_update_full)
 __global__ __launch_bounds__(64, 2) void step_kernel_ram_fullr(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
                                                                const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                                                                const double *__restrict__ g_sharedR)
-{ step_body<true, false, false, false, true>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+{ step_body<StepRamFullr>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+inline auto step_entry(StepRamFullr) { return step_kernel_ram_fullr; }
 
 } // namespace mcx

@@ -47,6 +47,14 @@ __global__ __launch_bounds__(256) void svd_init_kernel(double *Vc, uint8_t *stat
 // keep their order, so do the bits.  A column is needed for wI consecutive steps: it enters a ring of wI + 2 LDS columns one step ahead and
 // leaves it for global memory the step after its last pair.  This form (npar 201..256): each wave holds six octets and sixteen loader
 // lanes; the loaders' global loads (issued one step before they write the ring) and stores run under the wave's own pair arithmetic.
+// The three kernels' LDS is the ring: `cols` columns of `stride` doubles.  Columns: the b pair-lanes' + 2 where loader lanes bring a
+// column in a step ahead and take it out a step after its last pair (svd_sweep_stream_kernel), + 1 where a leaving column hands its slot to
+// the entering one inside one thread (the two stream32 kernels, b = 32).  Stride of the sweeps: every octet row 8 u + oj, u < RL, exists,
+// + 2 (= 2 mod 4); of svd_applyv_stream32_kernel: its two row groups of 2 RP + 2 doubles + 2 (half of it odd).
+MCX_HD constexpr int svd_ring_cols(int b, bool loaders) { return b + (loaders ? 2 : 1); }
+MCX_HD constexpr int svd_ring_ls(int RL) { return 8 * RL + 2; }
+MCX_HD constexpr int svd_ring_slot(int RP) { return 4 * RP + 6; }
+MCX_HD constexpr size_t svd_ring_lds(int cols, int stride) { return (size_t)cols * stride * sizeof(double); }
 #ifndef MCX_SVDS_WAVES
 #define MCX_SVDS_WAVES 3                                     // waves per SIMD asked for up to npar 208 (RL 26)
 #endif
@@ -63,9 +71,9 @@ __global__ __launch_bounds__(256, (RL <= 26 ? MCX_SVDS_WAVES : 2)) void svd_swee
     mcx_d2 *log = rot + (size_t)chain * ((size_t)d * (d - 1) / 2);
     // ring column stride: every octet row 8 u + oj exists (rows >= npar hold zeros: they add nothing to the three sums and rotate to zero
     // -- no bounds tests in the loop); = 2 mod 4
-    constexpr int LS = 8 * RL + 2;
+    constexpr int LS = svd_ring_ls(RL);
     double *GY = S;                                            // the ring: RB columns
-    const int RB = b + 2;
+    const int RB = svd_ring_cols(b, true);
     const int nb = (d + b - 1) / b;
     const int wv = tid >> 6, ln = tid & 63;
     const bool loader = ln >= 48;
@@ -175,9 +183,9 @@ __global__ __launch_bounds__(256, MCX_SVDS_WAVES) void svd_sweep_stream32_kernel
     mcx_d2 *log = rot + (size_t)chain * ((size_t)d * (d - 1) / 2);
     // ring column stride: every octet row 8 u + oj exists (rows >= npar hold zeros: they add nothing to the three sums and rotate to zero
     // -- no bounds tests in the loop); = 2 mod 4
-    constexpr int LS = 8 * RL + 2;
+    constexpr int LS = svd_ring_ls(RL);
     double *GY = S;                                            // the ring: RB columns
-    constexpr int b = 32, RB = b + 1;
+    constexpr int b = 32, RB = svd_ring_cols(b, false);
     const int nb = (d + b - 1) / b;
     const int ol = tid >> 3, oj = tid & 7;                     // pair-lane of this thread's octet, partial chain / row residue
     // ... and every thread moves element `tid` of the columns on their way in and out
@@ -276,8 +284,8 @@ __global__ __launch_bounds__(64) void svd_applyv_stream32_kernel(double *Vc, con
     double *V = Vc + (size_t)chain * d * d;
     const mcx_d2 *log = rot + (size_t)chain * ((size_t)d * (d - 1) / 2);
     // doubles per row group (its odd last row at 2 RP) and per ring column (SLOT / 2 odd: 16 lanes on 16 columns, 64 banks)
-    constexpr int RGS = 2 * RP + 2, SLOT = 4 * RP + 6;
-    constexpr int b = 32, RB = b + 1;
+    constexpr int RGS = 2 * RP + 2, SLOT = svd_ring_slot(RP);
+    constexpr int b = 32, RB = svd_ring_cols(b, false);
     const int nb = (d + b - 1) / b;
     const int ln = threadIdx.x, rg = ln >> 5, rl = ln & 31, rk0 = 2 * wv + rg;
     const int lu = rl;                                         // ... and row pair `rl` (rl < RP) of the columns on their way in and out

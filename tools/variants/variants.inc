@@ -15,9 +15,9 @@ static int variant_env(const char *name) { const char *e = getenv(name); return 
 static bool variant_pooled_ok(const mcmcx_engine *h) { return h->plan.pooled_mfma && !h->dodr && h->d >= 17 && h->d <= 64; }
 #define MCX_VARIANT_STEP_ENTRIES \
     {"step", "pooled_mfma3_kernel", [](const mcmcx_engine *h) { return variant_pooled_ok(h) && variant_env("MCMCX_POOLED_WAVES") == 4; }, \
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma3_kernel, dim3(2 * h->ntiles), dim3(64), pooled_mfma_lds(h->d) / 2, STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT}, \
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma3_kernel, dim3(2 * h->ntiles), dim3(64), PooledMfmaLds(h->d).bytes / 2, STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT}, \
     {"step", "pooled_mfma2_kernel", [](const mcmcx_engine *h) { return variant_pooled_ok(h) && variant_env("MCMCX_POOLED_WAVES") == 3; }, \
-     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma2_kernel, dim3(h->ntiles), dim3(128), pooled_mfma_lds(h->d), STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT}, \
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(pooled_mfma2_kernel, dim3(h->ntiles), dim3(128), PooledMfmaLds(h->d).bytes, STEP_ARGS, STEP_TGT, h->pool.d_RT); }, SH_RT}, \
     {"step", "step_kernel<false, true, false>", [](const mcmcx_engine *h) { return !h->pooled && kernel_method(h) != M_RAM && h->dodr && !phased(h) && variant_env("MCMCX_DR_GENERAL") == 1; }, \
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel<false, true, false>), G1, lds_step(h), STEP_ARGS, STEP_RS, STEP_TGT, h->E.sharedR); }},
 static bool variant_svd_sweep(hipStream_t stream, double *Gc, mcx_d2 *rot, uint8_t *state, int *anyrot, int nlanes, int d, size_t lss)
