@@ -787,6 +787,13 @@ int64_t mcmcx_debug_quant_key(double x, int32_t inverse);
  * mcx_api.hip), entry `index` as "family:name" into buf -- the name mcmcx_last_kernel reports after a run.  Returns the number
  * of entries (index = -1, buf = NULL: count only).  Needs no device.  tests/test_kernel_table.py requires a parity test per entry. */
 int mcmcx_debug_kernel_table(int32_t index, char *buf, int32_t len);
+/* The template instance(s) the last mcmcx_run launched for the step, joined by '+', into buf: a group entry stands for one instance
+ * per (group width, npar rounded up, delayed-rejection form, target kind) -- "group_step_kernel<16,20,0,gauss>",
+ * "group_step_kernel<4,8,1,any>" (the general delayed-rejection form takes its target at run time),
+ * "group_step_kernel<16,20,2,banana>+group_step_kernel<16,20,1,any>" (the power-of-two form queues both), "group_ram_kernel<32>";
+ * every other entry is the name mcmcx_last_kernel reports, and "" before the first run.  Read-only, nothing is launched.  Refused with
+ * -57, nothing written: a null h or buf, a len too small. */
+int mcmcx_debug_last_instance(mcmcx_handle h, char *buf, int32_t len);
 /* every chain's SVD proposal factor (per-chain mode, condmax > 0) replaced by R (column-major d x d; scam: the rotation)
  * and qcovstd (scam; NULL = keep): a test feeds the factors an external dgesvd returned at an adaptation */
 int mcmcx_debug_set_factor(mcmcx_handle h, const double *R_colmajor, const double *qcovstd);

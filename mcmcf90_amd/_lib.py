@@ -164,6 +164,8 @@ SYMBOLS["mcmcx_debug_symsvd"] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_
 # the tick's own factorisation on a caller's covariances, in the engine's instances; the host's statement of it (tests)
 SYMBOLS["mcmcx_debug_calculate_R"] = (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_uint8), _IP, C.c_char_p, C.c_int32])
 SYMBOLS["mcmcx_debug_host_calculate_R"] = (C.c_int, [C.c_int32, _DP, _DP, _DP, _IP])
+# the template instance(s) behind the last run's table name (tests)
+SYMBOLS["mcmcx_debug_last_instance"] = (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32])
 # per-chain start points: given by the caller, or drawn on the device at init
 SYMBOLS["mcmcx_set_par0_all"] = (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32])
 SYMBOLS["mcmcx_set_par0_spread"] = (C.c_int, [C.c_void_p, C.c_double])

@@ -1447,6 +1447,18 @@ int mcmcx_debug_kernel_table(int32_t index, char *buf, int32_t len)
     return total;
 }
 
+// The template instance(s) behind the table name of the last run: the group launchers note theirs (launch_group_inst,
+// launch_group_ram_d4), every other entry is its own name.  Reads two fields of the handle; nothing is launched.
+int mcmcx_debug_last_instance(mcmcx_handle h, char *buf, int32_t len)
+{
+    const char *who = "mcmcx_debug_last_instance";
+    if (!h || !buf) return fail(-57, std::string(who) + ": null argument");
+    const std::string name = h->last_instance ? h->last_instance : mcmcx_last_kernel(h);
+    if (len < 1 || (size_t)len <= name.size()) return fail(-57, std::string(who) + ": len too small for \"" + name + "\"");
+    snprintf(buf, (size_t)len, "%s", name.c_str());
+    return 0;
+}
+
 int64_t mcmcx_debug_samples_offset(int64_t slot, int64_t ntiles, int64_t nfields, int64_t tile, int64_t field)
 {
     return (int64_t)samples_row((size_t)slot, (size_t)ntiles, (size_t)nfields, (size_t)tile, (size_t)field);

@@ -133,6 +133,9 @@ struct mcmcx_engine {
     int simuind = 0;
     // name of the sampling kernel launch_step / launch_scam ran last, or of pooled mode's phase form (mcmcx_last_kernel)
     const char *last_kernel = "";
+    // ... and, where an entry stands for several template instances (the group kernels), the instance(s) it launched, joined by '+'
+    // (mcmcx_debug_last_instance); nullptr: the entry's own name
+    const char *last_instance = nullptr;
     std::string launch_err;             // set by a launcher that found no kernel for the configuration: the run fails with it
     // host copies of the problem
     std::vector<double> par0, cmat0;                 // cmat0 col-major d*d

@@ -76,6 +76,7 @@ static void launch_entry(mcmcx_engine *h, const KernelEntry *e, const char *fami
 {
     if (!e) { h->launch_err = std::string("no ") + family + " kernel covers this configuration"; return; }
     h->last_kernel = e->name;
+    h->last_instance = nullptr;                           // (a launcher that stands for several template instances names the one it takes)
     e->launch(h, it0, it1);
 }
 // ---- the lane-group step kernel (mcx_group.hpp): four chains per wave, factors in registers
@@ -122,6 +123,12 @@ static bool group_wins(const mcmcx_engine *h, int drm, int gw)
     if (gw == 4) return h->dodr ? (drm == 2 || n <= 131072) : (d >= 11 || n <= 131072);
     return d >= 11 || (h->dodr && d >= 9 && n <= 131072);
 }
+// an instance's name for mcmcx_debug_last_instance, from the template parameters themselves: "group_step_kernel<16,20,2,gauss>"
+static std::string group_inst_name(int gw, int d4, int drm, int tk)
+{
+    const char *t = tk == TGT_GAUSS ? "gauss" : tk == TGT_BANANA ? "banana" : tk == TGT_EXPDATA ? "expdata" : "any";
+    return "group_step_kernel<" + std::to_string(gw) + "," + std::to_string(d4) + "," + std::to_string(drm) + "," + t + ">";
+}
 // one instantiation per (group width, npar rounded up, delayed-rejection form, target kind); DRM 0 = none, 1 = the general form (R, R2, iC
 // in registers), 2 = drscale a power of two (no R2; iC in LDS): the instantiation without R2 runs unless the device flag says that some
 // factor leaves the range in which R'z / drscale is R2'z bit for bit; the general one is queued behind the same flag and returns at once
@@ -131,6 +138,10 @@ static void launch_group_inst(mcmcx_engine *h, int it0, int it1)
 {
     const dim3 g(h->ntiles * (GW == 16 ? 16 : 4)), b(64);           // 64 / GW chains per wave
     const double *lam = h->E.tgt.lamT;
+    // what the branches below launch, in their order (a refusal fails the run whatever the name says)
+    static const std::string inst = DRM == 0 ? group_inst_name(GW, D4, 0, TK) : DRM == 1 ? group_inst_name(GW, D4, 1, -1)
+        : group_inst_name(GW, D4, 2, TK) + "+" + group_inst_name(GW, D4, 1, -1);
+    h->last_instance = inst.c_str();
     if constexpr (DRM != 0 && D4 > GROUP_MAX_NPAR_DR) h->launch_err = "group kernel: no delayed-rejection instantiation above npar " +
         std::to_string(GROUP_MAX_NPAR_DR);
     else if constexpr (TK == TGT_EXPDATA && D4 != 4) h->launch_err = "group kernel: the expdata target has two parameters";
@@ -269,6 +280,8 @@ static bool ram_group_covers(const mcmcx_engine *h)
 template <int D4>
 static void launch_group_ram_d4(mcmcx_engine *h, int it0, int it1)
 {
+    static const std::string inst = "group_ram_kernel<" + std::to_string(D4) + ">";
+    h->last_instance = inst.c_str();
     hipLaunchKernelGGL((group_ram_kernel<D4, -1>), dim3(h->ntiles * 16), dim3(64), 0, h->stream, h->E, it0, it1,
         (const double *)h->d_ramscale, h->E.tgt.lamT, h->d_accb);
 }

@@ -985,6 +985,13 @@ class Engine:
         """Name of the sampling kernel the last run() launched (mcmcx_last_kernel)."""
         return (self.L.mcmcx_last_kernel(self.h) or b"").decode()
 
+    def last_instance(self):
+        """Test probe (mcmcx_debug_last_instance): the template instance(s) the last run() launched for the step, joined by '+' --
+        'group_step_kernel<16,20,2,gauss>+group_step_kernel<16,20,1,any>', 'group_ram_kernel<32>'; elsewhere last_kernel()'s name."""
+        buf = C.create_string_buffer(256)
+        self._chk(self.L.mcmcx_debug_last_instance(self.h, buf, 256))
+        return buf.value.decode()
+
     def kernel_time(self, reset=False):
         ms, nl, ns = C.c_double(), C.c_int64(), C.c_int64()
         self._chk(self.L.mcmcx_kernel_time(self.h, C.byref(ms), C.byref(nl), C.byref(ns), int(reset)))

@@ -115,6 +115,30 @@ def test_group_kernels_hold_no_v_cmpx(device_disassembly):
     assert seen >= 10 and not bad, (seen, bad[:3])
 
 
+def test_group_instance_table_is_the_compiled_set(device_disassembly):
+    """tests/test_gpu_group_instances.py runs every row of its literal table INSTANCES at both ends of the row's npar range; here that table is
+    held to the kernel symbols of the shipped code object (the labels of the disassembly, not the instructions): the integer template arguments
+    of every group_step_kernel<GW, D4, DRM, TK> (a negative TK is mangled as Lin1E) must be the table's rows, no more and no fewer -- a newly
+    instantiated size fails here until it has cases, and so does a row that is no longer compiled.  group_ram_kernel<D4, -1> is compiled for
+    the four sizes tests/test_gpu_ram_every_chain.py runs at 16 / 17, 32 / 33, 56 / 57 and 64."""
+    import test_gpu_group_instances as gi
+    num = lambda s: -int(s[1:]) if s.startswith("n") else int(s)
+    step, ram = set(), set()
+    for line in device_disassembly:
+        if not line.endswith(">:"):
+            continue
+        ms = re.search(r"group_step_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(n?\d+)EE", line)
+        mr = re.search(r"group_ram_kernelILi(\d+)ELi(n?\d+)EE", line)
+        if ms:
+            step.add(tuple(num(g) for g in ms.groups()))
+        if mr:
+            ram.add(tuple(num(g) for g in mr.groups()))
+        assert ms or mr or not ("group_step_kernel" in line or "group_ram_kernel" in line), line      # (an instance this test cannot decode)
+    want = gi.compiled_set()
+    assert step == want, (sorted(step - want), sorted(want - step))
+    assert ram == {(16, -1), (32, -1), (56, -1), (64, -1)}, sorted(ram)
+
+
 def _vregs(op):
     op = op.strip().rstrip(",")
     m = re.match(r"^v\[(\d+):(\d+)\]$", op)

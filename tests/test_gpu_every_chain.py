@@ -368,14 +368,16 @@ def test_every_chain_of_a_form_equals_the_oracle(oracle, monkeypatch, prob, kern
     assert not failures, "; ".join(failures)
 
 
-def _run_and_compare(e, o, ckw, nch, cuts, kernel, edge=False, cols=False):
+def _run_and_compare(e, o, ckw, nch, cuts, kernel, edge=False, cols=False, instance=None):
     """Run an initialised engine through the cuts, asserting the kernel after each; read every chain, close the engine, and compare every quantity
     on every chain with the oracle's (_pack).  Returns one line per quantity that differs, with the first failing chains.  (tests/test_gpu_accept_extremes.py
-    runs its chains through this too: there o carries the expected status bits, and method = 'ram' keeps no covariance.)"""
+    runs its chains through this too: there o carries the expected status bits, and method = 'ram' keeps no covariance.  tests/test_gpu_group_instances.py
+    names the template instance(s) behind the table entry as well.)"""
     nsimu, ram = ckw["nsimu"], ckw["method"] == "ram"
     for upto in cuts:
         e.run(upto)
         assert e.last_kernel() == kernel, e.last_kernel()
+        assert instance is None or e.last_instance() == instance, e.last_instance()
     assert e.simuind == nsimu
     theta, masks, scal = e.theta(), e.accept_masks(), e.scalars()
     rng = np.array([e.rng(c)[0] for c in range(nch)], dtype=np.uint64)
