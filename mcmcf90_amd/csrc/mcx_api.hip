@@ -463,6 +463,7 @@ static int init_chains(mcmcx_engine *h, const InitialFactor &f)
     if ((rc = dev_alloc(h, &E.zs, L * 2 * d))) return rc;
     if ((rc = h->plan.cs_mapped ? host_alloc(h, &E.cs, L * 2 * d) : dev_alloc(h, &E.cs, L * 2 * d))) return rc;
     if (h->plan.xscr && (rc = dev_alloc(h, &E.xscr, L * 2 * d))) return rc;
+    if (h->plan.ram_pair && (rc = dev_alloc(h, &h->d_pair, L * 3 * d))) return rc;
     if ((rc = dev_alloc(h, &E.scal, L * NSCAL))) return rc;
     if ((rc = dev_alloc(h, &E.ictr, L * NICTR))) return rc;
     if ((rc = dev_alloc(h, &E.rngn, L))) return rc;

@@ -246,6 +246,13 @@ constexpr int RW = MCX_RW;  // panel width of the RAM sweep (d = 50: five full p
 #define MCX_RW_WIDE 17
 #endif
 constexpr int RW_WIDE = MCX_RW_WIDE, RAM_SMALL_MAX = 20;
+// ... and of its sweep that applies two updates in one pass (ram_update_pair): two work vectors per column, so equal panels of at most ten
+// (npar 50: five of 10).  Measured at the headline, ms per 100 iterations against 440.7 with every sweep storing: 9 columns 411.6,
+// 10 397.4, 13 414.1 (profiles/r27_a)
+#ifndef MCX_RW_PAIR
+#define MCX_RW_PAIR 10
+#endif
+constexpr int RW_PAIR = MCX_RW_PAIR;
 MCX_DEV int ram_panel_width(int d, int rwmax) { const int np = (d + rwmax - 1) / rwmax; return (d + np - 1) / np; }
 constexpr int TW = MCX_TW;  // panel width of the per-chain triangular product
 

@@ -26,7 +26,7 @@ struct mcx_switches {
     int pooled_mfma_dr_min = -1, pooled_scalar = -1, dr_big = -1, scam_pooled_16 = -1, scam_fast_lanes = -1, scam_waves = -1,
         svd_lane = -1, cov_batch_rows = -1, ram_wide = -1, pooled_waves = -1, pooled_ks = -1, cols_phased = -1, host_mapped = -1,
             host_fuse = -1, lds_scratch = -1, group = -1, group_dr2 = -1, group_gw = -1, ram_group = -1, tile_factor = -1,
-            pooled_phase_mfma = -1;
+            pooled_phase_mfma = -1, ram_pair = -1;
     static int get(const char *name) { const char *e = getenv(name); return e ? atoi(e) : -1; }
     void read()
     {
@@ -37,7 +37,7 @@ struct mcx_switches {
         cols_phased = get("MCMCX_COLS_PHASED"); host_mapped = get("MCMCX_HOST_MAPPED"); host_fuse = get("MCMCX_HOST_FUSE");
         lds_scratch = get("MCMCX_LDS_SCRATCH"); group = get("MCMCX_GROUP"); group_dr2 = get("MCMCX_GROUP_DR2");
         group_gw = get("MCMCX_GROUP_GW"); ram_group = get("MCMCX_RAM_GROUP"); tile_factor = get("MCMCX_TILE_FACTOR");
-        pooled_phase_mfma = get("MCMCX_POOLED_PHASE_MFMA");
+        pooled_phase_mfma = get("MCMCX_POOLED_PHASE_MFMA"); ram_pair = get("MCMCX_RAM_PAIR");
     }
 };
 // the plain lane step's LDS form (EngineDev::lds_scratch): nothing, the state and scratch vectors (step_kernel_ldsv), those and the packed
@@ -97,6 +97,8 @@ struct KernelPlan {
     // rotation
     int pooled_phase = 0;
     bool ram_wide = false;              // method = 'ram' above RAM_SMALL_MAX through step_kernel_ram_wide
+    // ... whose update-only waves store the factor once per two iterations (ram_update_pair; [3 npar] more scratch doubles per chain)
+    bool ram_pair = false;
     bool scam_pooled12 = false, scam_fast_tile = false; int scam_waves = 1;
     bool am = false;                    // the per-chain adaptation (not RAM, not pooled): covariance, mean and factor scratch per chain
     bool xscr = false;                  // the chains' global scratch vectors (EngineDev::xscr): pooled DR, or npar > 320
@@ -189,6 +191,7 @@ struct mcmcx_engine {
     EngineDev E{};
     std::vector<void *> allocs;
     double *d_ramscale = nullptr, *d_moments = nullptr;
+    double *d_pair = nullptr;           // KernelPlan::ram_pair: [3 npar] scratch doubles per chain (step_kernel_ram_wide's pair_scr)
     void *d_scratch = nullptr; size_t scratch_cap = 0;  // the sample store's readers' scratch, in bytes (samples_scratch): grows only
     // blocked SVD of the adaptation (large npar)
     double *d_Gc = nullptr, *d_Vc = nullptr, *d_svc = nullptr; uint8_t *d_need = nullptr, *d_state = nullptr; int *d_anyrot = nullptr;

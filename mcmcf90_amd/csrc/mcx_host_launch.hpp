@@ -351,7 +351,7 @@ static const KernelEntry STEP_TABLE[] = {
      [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRamLdsr, STEP_RS, STEP_TGT, h->E.sharedR); }},
     {"step", "step_kernel_ram_wide", [](const mcmcx_engine *h) {
         return kernel_method(h) == M_RAM && h->d > RAM_SMALL_MAX && h->plan.ram_wide; },
-     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRamWide, STEP_RS, STEP_TGT, h->E.sharedR); }},
+     [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRamWide, STEP_RS, STEP_TGT, h->d_pair); }},
     {"step", "step_kernel<true, false, false>", [](const mcmcx_engine *h) { return kernel_method(h) == M_RAM; },
      [](mcmcx_engine *h, int it0, int it1) { STEP_LAUNCH(StepRam, STEP_RS, STEP_TGT, h->E.sharedR); }},
     // ---- delayed rejection, per-chain factors: the second stage's two vectors in global scratch / in LDS
@@ -590,6 +590,8 @@ static void plan_kernels(mcmcx_engine *h)
     p.pooled_two_waves = pooled_two_waves(h, sw);
     p.pooled_forty_rows = pooled_forty_rows(h, sw);
     p.ram_wide = sw.ram_wide != 0;
+    // (MCMCX_RAM_PAIR=0: every update sweep stores the factor -- the A/B form, and the one the tests compare with)
+    p.ram_pair = p.ram_wide && sw.ram_pair != 0;
     p.scam_pooled12 = scam_use_12(h, sw);
     p.scam_fast_tile = scam_fast_tile_kernel(h, sw);
     p.scam_waves = scam_tile_waves(h, sw);
@@ -629,6 +631,7 @@ static void plan_kernels(mcmcx_engine *h)
     else if (c.method == MCMCX_METHOD_SCAM) p.scam = pick_entry(h, SCAM_TABLE, sizeof(SCAM_TABLE) / sizeof(SCAM_TABLE[0]));
     else if (p.group_d4) p.step = pick_entry(h, GROUP_TABLE, sizeof(GROUP_TABLE) / sizeof(GROUP_TABLE[0]));
     else p.step = pick_entry(h, STEP_TABLE, sizeof(STEP_TABLE) / sizeof(STEP_TABLE[0]));
+    p.ram_pair = p.ram_pair && p.step && std::strcmp(p.step->name, "step_kernel_ram_wide") == 0;      // (only that kernel pairs)
     // pooled mode: the shared layouts that entry reads (no R2 / iC without DR; the lane kernels read the SVD factor in the dense layout)
     const KernelEntry *e = c.method == MCMCX_METHOD_SCAM ? p.scam : p.step;
     p.shared = (h->pooled && e) ? e->shared & (h->dodr ? ~0u : ~(unsigned)(SH_DR | SH_DRT)) : 0;

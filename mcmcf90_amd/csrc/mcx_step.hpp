@@ -33,11 +33,17 @@ constexpr int NLC = MCX_NLC;     // 19 rows x 2 doubles x 64 lanes = 19 456 B pe
 // takes longer than read all + write all), so in such a wave every lane stores in both sweeps -- the lanes a sweep does
 // not concern store the value they loaded -- and each sweep writes whole segments.  A wave of one kind (the bench's
 // default start: no downdates) takes the other instantiation, whose update sweep stores from inside its own branch.
-template <bool MIXED, int RWT = RW>
+// SWEEP (update-only waves of step_kernel_ram_wide): SW_DEFER is the update sweep without its factor stores -- it
+// keeps EVERY row's rotation and parks its work vector x in xp_t, and the next iteration's ram_update_pair applies both updates in one
+// pass; SW_FLUSH is the plain sweep with x taken back from xp_t (the same operations on the same factor: the same bits), for a deferred
+// update whose successor turns out to hold a downdate lane.
+enum { SW_PLAIN = 0, SW_DEFER = 1, SW_FLUSH = 2 };
+template <bool MIXED, int RWT = RW, int SWEEP = SW_PLAIN>
 MCX_DEV bool ram_update(double *Rt, const double *zc_t, const double *zn_t, double *cs_t, double *P_t,
                         const double *theta_t, int lane, int d, double a, double su, bool act, bool fuse, uint32_t &status,
-                        double *lc, bool &pdesc)
+                        double *lc, bool &pdesc, double *xp_t = nullptr)
 {
+    static_assert(SWEEP == SW_PLAIN || !MIXED, "a deferred update belongs to a wave of update lanes");
     const bool up = act && (a >= 0.0);
     const bool down = act && !(a >= 0.0);
     const int rwe = (RWT == RW) ? RW : ram_panel_width(d, RWT);       // RW: panels of ten (the last one narrower); wide: equal panels
@@ -53,7 +59,15 @@ MCX_DEV bool ram_update(double *Rt, const double *zc_t, const double *zn_t, doub
                 double xa[RWT], P[RWT];
 #pragma unroll
                 // x = u/sum(u**2)*a
-                for (int u = 0; u < RWT; ++u) { xa[u] = up ? GV(zc_t, J0 + (u < nw ? u : nw - 1)) / su * a : 0.0; P[u] = 0.0; }
+                for (int u = 0; u < RWT; ++u) {
+                    if (SWEEP == SW_FLUSH) xa[u] = GV(xp_t, J0 + (u < nw ? u : nw - 1));
+                    else xa[u] = up ? GV(zc_t, J0 + (u < nw ? u : nw - 1)) / su * a : 0.0;
+                    P[u] = 0.0;
+                }
+                if (SWEEP == SW_DEFER) {
+#pragma unroll
+                    for (int u = 0; u < RWT; ++u) if (u < nw) GV(xp_t, J0 + u) = xa[u];
+                }
 if (MIXED) {
                     // next row's loads before this row's stores (see sweep B)
                     // (c, s) of an update lane or the substitution's a_i of a downdate lane, and z_next: one row ahead as well
@@ -110,7 +124,7 @@ if (MIXED) {
                             for (int u = 0; u < RWT; ++u) {
                                 double t = c * r[u] + sn * xa[u];
                                 xa[u] = c * xa[u] - sn * r[u];
-                                if (u < nw) STNT(seg, u, t);
+                                if (SWEEP != SW_DEFER && u < nw) STNT(seg, u, t);
                                 P[u] = dfma(t, zi, P[u]);
                             }
                         } else {
@@ -133,17 +147,17 @@ if (MIXED) {
                         const double zi = fuse ? GV(zn_t, i) : 0.0;
                         double rr, c, sn;
                         d_rotg(GV(seg, 0), xi, rr, c, sn);
-                        GV(seg, 0) = rr;
+                        if (SWEEP != SW_DEFER) GV(seg, 0) = rr;
                         if (lc && i < NLC) { lc[(2 * i) * 64 + lane] = c; lc[(2 * i + 1) * 64 + lane] = sn; }
                         // (the last panel's rotations have no later panel to serve)
-                        else if (J0 + nw < d) { GV(cs_t, 2 * i) = c; GV(cs_t, 2 * i + 1) = sn; }
+                        else if (SWEEP == SW_DEFER || J0 + nw < d) { GV(cs_t, 2 * i) = c; GV(cs_t, 2 * i + 1) = sn; }
 #pragma unroll
                         for (int u = 0; u < RWT; ++u) {
                             const bool off = (u > ui) && (u < nw);
                             double t = c * r[u] + sn * xa[u];
                             double nx = c * xa[u] - sn * r[u];
                             xa[u] = off ? nx : xa[u];
-                            if (!MIXED) { if (off) STNT(seg, u - ui, t); }
+                            if (!MIXED) { if (SWEEP != SW_DEFER && off) STNT(seg, u - ui, t); }
                             else r[u] = off ? t : r[u];
                             double tp = (u == ui) ? rr : t;
                             double np = dfma(tp, zi, P[u]);
@@ -318,6 +332,94 @@ if (MIXED) {
 #undef CS_
 }
 
+// Two cholupdates in one pass over the factor (iteration k deferred by SW_DEFER, iteration k + 1 = this one; update lanes only).  Per
+// column panel two work vectors: xa0, iteration k's x as parked in xp_t, and xa1 = this iteration's x.  A row above the diagonal block
+// goes through iteration k's rotation (c0, s0: LDS rows < NLC, cs_t above -- what SW_DEFER left there), then through this one's (c1, s1:
+// c2_t, written by the diagonal blocks of the panels before); a diagonal element generates both rotations anew, the second from the
+// first one's result.  Every element sees LINPACK's operations in LINPACK's order, twice; the proposal accumulates from the final rows.
+#ifndef MCX_PAIR_UNROLL
+#define MCX_PAIR_UNROLL 1            // rows above the diagonal block, rows per trip: 2 costs 0.8 % at the headline (400.5 against 397.4 ms)
+#endif
+template <int RWP>
+MCX_DEV bool ram_update_pair(double *Rt, const double *zc_t, const double *zn_t, const double *cs_t, double *c2_t, const double *xp_t,
+                             double *P_t, const double *theta_t, int lane, int d, double a, double su, bool fuse, const double *lc,
+                             bool &pdesc)
+{
+    const int rwe = ram_panel_width(d, RWP);
+    for (int J0 = 0; J0 < d; J0 += rwe) {
+        const int nw = (d - J0) < rwe ? (d - J0) : rwe;
+        double xa0[RWP], xa1[RWP], P[RWP];
+#pragma unroll
+        // x = u/sum(u**2)*a
+        for (int u = 0; u < RWP; ++u) {
+            xa0[u] = GV(xp_t, J0 + (u < nw ? u : nw - 1));
+            xa1[u] = GV(zc_t, J0 + (u < nw ? u : nw - 1)) / su * a;
+            P[u] = 0.0;
+        }
+#pragma unroll MCX_PAIR_UNROLL
+        for (int i = 0; i < J0; ++i) {                               // rows above the diagonal block
+            double *seg = Rt + (size_t)(rowstart(i, d) + J0 - i) * 64;
+            double r[RWP];
+#pragma unroll
+            for (int u = 0; u < RWP; ++u) r[u] = LDNT(seg, u < nw ? u : nw - 1);
+            const bool inl = lc && i < NLC;
+            const double c0 = inl ? lc[(2 * i) * 64 + lane] : GV(cs_t, 2 * i);
+            const double s0 = inl ? lc[(2 * i + 1) * 64 + lane] : GV(cs_t, 2 * i + 1);
+            const double c1 = GV(c2_t, 2 * i), s1 = GV(c2_t, 2 * i + 1);
+            const double zi = fuse ? GV(zn_t, i) : 0.0;
+#pragma unroll
+            for (int u = 0; u < RWP; ++u) {
+                double t0 = c0 * r[u] + s0 * xa0[u];
+                xa0[u] = c0 * xa0[u] - s0 * r[u];
+                double t1 = c1 * t0 + s1 * xa1[u];
+                xa1[u] = c1 * xa1[u] - s1 * t0;
+                if (u < nw) STNT(seg, u, t1);
+                P[u] = dfma(t1, zi, P[u]);
+            }
+        }
+        for (int i = J0; i < J0 + nw; ++i) {                         // diagonal block
+            double *seg = Rt + (size_t)rowstart(i, d) * 64;
+            const int ui = i - J0, m = d - 1 - i;
+            double r[RWP];
+#pragma unroll
+            for (int u = 0; u < RWP; ++u) { int k = u - ui; k = k < 0 ? 0 : k; k = k > m ? m : k; r[u] = LDNT(seg, k); }
+            double xi0 = xa0[0], xi1 = xa1[0];
+#pragma unroll
+            for (int u = 1; u < RWP; ++u) { xi0 = (u == ui) ? xa0[u] : xi0; xi1 = (u == ui) ? xa1[u] : xi1; }
+            const double zi = fuse ? GV(zn_t, i) : 0.0;
+            double rr0, c0, s0, rr1, c1, s1;
+            d_rotg(GV(seg, 0), xi0, rr0, c0, s0);
+            d_rotg(rr0, xi1, rr1, c1, s1);
+            GV(seg, 0) = rr1;
+            // (the last panel's rotations have no later panel to serve)
+            if (J0 + nw < d) { GV(c2_t, 2 * i) = c1; GV(c2_t, 2 * i + 1) = s1; }
+#pragma unroll
+            for (int u = 0; u < RWP; ++u) {
+                const bool off = (u > ui) && (u < nw);
+                double t0 = c0 * r[u] + s0 * xa0[u];
+                double nx0 = c0 * xa0[u] - s0 * r[u];
+                double t1 = c1 * t0 + s1 * xa1[u];
+                double nx1 = c1 * xa1[u] - s1 * t0;
+                xa0[u] = off ? nx0 : xa0[u];
+                xa1[u] = off ? nx1 : xa1[u];
+                if (off) STNT(seg, u - ui, t1);
+                double tp = (u == ui) ? rr1 : t1;
+                double np = dfma(tp, zi, P[u]);
+                P[u] = (u >= ui && u < nw) ? np : P[u];
+            }
+        }
+        if (fuse) {                                                  // next candidate = theta + R_new' z_next (MCMC_DRAM.F90:29)
+            double th[RWP];                                           // the state's loads before the candidate's stores (see copy_vec)
+#pragma unroll
+            for (int u = 0; u < RWP; ++u) th[u] = GV(theta_t, J0 + (u < nw ? u : nw - 1));
+#pragma unroll
+            for (int u = 0; u < RWP; ++u) if (u < nw) GV(P_t, J0 + u) = th[u] + P[u];
+        }
+    }
+    pdesc = false;
+    return fuse;
+}
+
 // The same adaptation on a FULL column-major factor (condmax > 0: R is the d x d SVD factor U sqrt(s) 2.4/sqrt(d) of
 // covtor, and MCMC_adapt_ram hands it to dchud / dchdd as it is, MCMC_run_ram.F90:168-172).  LINPACK only touches
 // R(i,j), i <= j; the proposal matmulx(R,u) (MCMC_run_ram.F90:96-97) goes on using the whole matrix.  Plain column
@@ -458,6 +560,7 @@ struct StepForm {
     static constexpr bool LDSR = false;              // flat); ... and the chain's packed factor too
     static constexpr bool XG = false;                // DR: the quadratic forms' two vectors in the tile's global scratch (E.xscr), not LDS
     static constexpr int RWT = RW;                   // ram_update's panel width
+    static constexpr int RWP = 0;                    // ram_update_pair's panel width; 0: the form defers no update
 };
 template <bool RAM_, bool DR_, bool POOLED_>
 struct StepFlags : StepForm {
@@ -468,7 +571,7 @@ using StepRam = StepFlags<true, false, false>;
 using StepPooled = StepFlags<false, false, true>;
 struct StepLdsv : StepPlain { static constexpr bool LDSV = true; };
 struct StepLdsr : StepLdsv { static constexpr bool LDSR = true; };
-struct StepRamWide : StepRam { static constexpr int RWT = RW_WIDE; };
+struct StepRamWide : StepRam { static constexpr int RWT = RW_WIDE, RWP = RW_PAIR; };
 struct StepRamLdsr : StepRam { static constexpr bool LDSR = true; };
 struct StepRamFullr : StepRam { static constexpr bool WIDE_T = false, FULLR = true; };
 struct StepPooledDr : StepFlags<false, true, true> {};
@@ -503,10 +606,11 @@ template <class F>
 MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__restrict__ ramscale,
                        const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
                        const double *__restrict__ g_sharedR, const double *__restrict__ g_sharedR2 = nullptr,
-                       const double *__restrict__ g_sharediC = nullptr)
+                       const double *__restrict__ g_sharediC = nullptr, double *pair_scr = nullptr)
 {
     constexpr bool RAM = F::RAM, DR = F::DR, POOLED = F::POOLED, WIDE_T = F::WIDE_T, FULLR = F::FULLR, XG = F::XG;
-    constexpr int RWT = F::RWT;
+    constexpr int RWT = F::RWT, RWP = F::RWP;
+    constexpr bool PAIR = RWP > 0;
     using L = StepLds<F>;
     constexpr bool ldsv = L::ldsv, ldsr = L::ldsr, ramr = L::ramr;
     extern __shared__ double Xlds[];
@@ -524,6 +628,10 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
     if (ldsr || ramr) { const double *Rg = E.R + (size_t)tile * E.P * 64; copy_vec(Rt, Rg, nullptr, lane, E.P); }
     double *Y = X + (size_t)d * 64;
     double *c2_t = cs_t;
+    // PAIR (KernelPlan::ram_pair; nullptr: off): a deferred update's x [d], and the rotations [2 d] of the iteration that completes it
+    double *xp_t = PAIR && pair_scr ? pair_scr + (size_t)tile * 3 * d * 64 : nullptr;
+    double *rot2_t = PAIR && pair_scr ? xp_t + (size_t)d * 64 : nullptr;
+    bool pending = false;                         // wave-uniform: the factor in memory lacks the last iteration's update
 
     Rng g;
     g.k0 = E.k0; g.k1 = E.chain_id0 + (uint32_t)(tile * 64 + lane);
@@ -547,6 +655,9 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
     for (int it = it0; it <= it1; ++it) {
         double *zc_t = ldsr ? zs_t : zs_t + (size_t)(it & 1) * d * 64;          // z of this iteration
         double *zn_t = ldsr ? zs_t : zs_t + (size_t)((it + 1) & 1) * d * 64;    // z of the next one
+#ifdef MCX_PAIR_DEBUG   // (a debug build's check) nothing but the pair or flush sweep reads the factor while an update is pending
+        if (PAIR && pending) assert(!FULLR && !E.usesvd && !__any(!have_p));
+#endif
         // ---- newpar = MCMC_propose(oldpar, R)
         if (POOLED) { if (E.usesvd) gemvN_shared(g_sharedR, zc_t, cand_t, theta_t, lane, d); else trmv_shared(g_sharedR, zc_t, cand_t,
             theta_t, lane, d); }
@@ -631,10 +742,24 @@ MCX_DEV void step_body(const EngineDev &E, int it0, int it1, const double *__res
             double a = ramscale[it - it0] * (alpha12 - E.alphatarget);
             downs += (a >= 0.0) ? 0u : 1u;
             if (FULLR) ram_update_full(E.Rf + (size_t)tile * d * d * 64, zc_t, cs_t, lane, d, a, su_c, true, status);   // condmax > 0
-            else if (__any(!(a >= 0.0)))                  // a wave with downdate lanes: whole-segment stores in both sweeps
+            else if (__any(!(a >= 0.0))) {                // a wave with downdate lanes: whole-segment stores in both sweeps
+                if (PAIR && pending) {                    // (the deferred update first: its proposal is this iteration's candidate)
+                    ram_update<false, RWT, SW_FLUSH>(Rt, zc_t, zn_t, cs_t, cand_t, theta_t, lane, d, 0.0, su_c, true, false, status,
+                        RAM ? X : nullptr, pdesc, xp_t);
+                    pending = false;
+                }
                 have_p = ram_update<true, RWT>(Rt, zc_t, zn_t, cs_t, cand_t, theta_t, lane, d, a, su_c, true, pre, status,
                     RAM ? X : nullptr, pdesc);
-            else have_p = ram_update<false, RWT>(Rt, zc_t, zn_t, cs_t, cand_t, theta_t, lane, d, a, su_c, true, pre, status,
+            } else if (PAIR && pending) {
+                have_p = ram_update_pair<PAIR ? RWP : 1>(Rt, zc_t, zn_t, cs_t, rot2_t, xp_t, cand_t, theta_t, lane, d, a, su_c, pre,
+                    RAM ? X : nullptr, pdesc);
+                pending = false;
+            // an update the next iteration of this launch will complete: that one adapts too, and no launch ends with an update pending
+            } else if (PAIR && xp_t && it + 1 <= it1 && !(it + 1 < E.burnintime && E.doburnin != 0)) {
+                have_p = ram_update<false, RWT, SW_DEFER>(Rt, zc_t, zn_t, cs_t, cand_t, theta_t, lane, d, a, su_c, true, pre, status,
+                    RAM ? X : nullptr, pdesc, xp_t);
+                pending = true;
+            } else have_p = ram_update<false, RWT>(Rt, zc_t, zn_t, cs_t, cand_t, theta_t, lane, d, a, su_c, true, pre, status,
                 RAM ? X : nullptr, pdesc);
         }
         su_c = su_n;
@@ -892,11 +1017,12 @@ __global__ __launch_bounds__(64, 2) void step_kernel_ram_ldsr(EngineDev E, int i
 inline auto step_entry(StepRamLdsr) { return step_kernel_ram_ldsr; }
 
 // method='ram' above npar 20: step_kernel<true, false, false> with the wide column panels (RW_WIDE above)
+// pair_scr: KernelPlan::ram_pair's scratch, [3 npar] rows of 64 doubles per tile, or nullptr (every update sweep stores the factor)
 __global__ __launch_bounds__(64, MCX_RAM_WAVES) void step_kernel_ram_wide(EngineDev E, int it0, int it1,
     const double *__restrict__ ramscale,
                                                      const double *__restrict__ g_mu, const double *__restrict__ g_lamT,
-                                                     const double *__restrict__ g_sharedR)
-{ step_body<StepRamWide>(E, it0, it1, ramscale, g_mu, g_lamT, g_sharedR); }
+                                                     double *pair_scr)
+{ step_body<StepRamWide>(E, it0, it1, ramscale, g_mu, g_lamT, nullptr, nullptr, nullptr, pair_scr); }
 inline auto step_entry(StepRamWide) { return step_kernel_ram_wide; }
 
 // pooled mode with delayed rejection: the shared factor, its second-stage copy R2 = R / drscale and the shared inverse
