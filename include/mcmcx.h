@@ -149,6 +149,37 @@ int mcmcx_set_target_expdata(mcmcx_handle h, int32_t ndata, const double *x, con
  * y = [nycol][ndata].  Device-resident; the iteration is cut at the evaluations like the host-callback path (several
  * short launches per iteration, no host round trip).  Give the nycol sigma2 / nobs with mcmcx_set_sigma2nobs. */
 int mcmcx_set_target_expdata_cols(mcmcx_handle h, int32_t ndata, int32_t nycol, const double *x, const double *y);
+/* ---- Many fits in one run: a data set per chain for the response-column target (no counterpart in the reference, whose one chain
+ * has one data set).  mcmcx_set_target_expdata_all is mcmcx_set_target_expdata_cols with every chain's own observations: the model is
+ * that call's, operation for operation -- ss_j = the fma chain from +0.0 over i ascending of r * r, r = y_j(i) - theta_1 exp(-(theta_{1+j}
+ * x_i)), npar = 1 + nycol -- and chain c is the reference's single chain on chain c's data: its stream (seed, chain_id0 + c), its
+ * factor and its counters are what the same chain has in a run with that one data set.  A run that does not make the call is bit for
+ * bit the run without it; every chain given the same data is the mcmcx_set_target_expdata_cols run.
+ *
+ * y_all is host memory, [nchains][nycol][ndata]; x is [ndata], shared by all chains, when x_per_chain = 0 and [nchains][ndata] when it
+ * is 1.  Both are copied at the call and not inspected: NaN and inf propagate as the arithmetic says.  The call composes with
+ * mcmcx_set_par0_all / _spread, mcmcx_set_bounds, mcmcx_set_priors, mcmcx_set_sigma2nobs (one sigma2 / nobs per column, shared by the
+ * chains) and mcmcx_set_samples, whose ss and sigma2 fields are then per fit; every method runs (dram with and without delayed
+ * rejection, ram, er, scam).  The last target setter called wins.
+ *
+ * Cost: device tables, tile-interleaved like every per-chain array and allocated only when the call was made,
+ *   y: ceil(nchains / 64) x nycol x ndata x 64 doubles, row j * ndata + i of a tile;
+ *   x: ceil(nchains / 64) x ndata x 64 doubles when x_per_chain = 1 (otherwise the shared x[ndata]);
+ * lanes of the last tile without a chain hold +0.0 (46 MB and 23 MB at 262 144 chains, nycol 2, ndata 11).  A wave's load of one
+ * element is one contiguous 512-byte segment.  The call's host copies live until mcmcx_init has filled the tables (init stages a
+ * tile-interleaved host vector of the same size for the upload); both are released there.
+ *
+ * mcmcx_chain_data_info, after init: out4 = {mode: 0 one data set for all chains, 1 y per chain, 2 x and y per chain; ndata; nycol;
+ * bytes of the per-chain device tables} (ndata and nycol: 0 for a target without data).  It is a getter and answers like the other
+ * getters: -40 for a null handle or one that is not inited, -1 for a null out4.
+ *
+ * mcmcx_set_target_expdata_all refuses with -58 (the reason in mcmcx_last_error), nothing allocated or launched and the handle's target
+ * unchanged: a null handle, x or y_all; nchains that differs from the handle's; ndata < 1; x_per_chain outside 0 .. 1; a call after
+ * mcmcx_init; pooled mode (one proposal factor pooled over different posteriors is not a method).  As in mcmcx_set_target_expdata_cols,
+ * nycol out of range is -21 and npar != 1 + nycol is -22. */
+int mcmcx_set_target_expdata_all(mcmcx_handle h, int32_t nchains, int32_t ndata, int32_t nycol, const double *x, int32_t x_per_chain,
+                                 const double *y_all /* [nchains][nycol][ndata] */);
+int mcmcx_chain_data_info(mcmcx_handle h, int64_t *out4);
 /* Host-callback target: the user's own ssfunction / priorfun / checkbounds (external_inc.h:4-33) behind plain C
  * signatures (the Fortran shim adapts the array-result / assumed-shape ABIs).  The engine calls them from the
  * thread that calls mcmcx_run, one chain after the other, at the points the reference does (MCMC_run.F90:47,55-56,

@@ -170,6 +170,9 @@ SYMBOLS["mcmcx_debug_last_instance"] = (C.c_int, [C.c_void_p, C.c_char_p, C.c_in
 SYMBOLS["mcmcx_set_par0_all"] = (C.c_int, [C.c_void_p, _DP, C.c_int32, C.c_int32])
 SYMBOLS["mcmcx_set_par0_spread"] = (C.c_int, [C.c_void_p, C.c_double])
 SYMBOLS["mcmcx_start_info"] = (C.c_int, [C.c_void_p, _LP])
+# many fits in one run: a data set per chain for the response-column target
+SYMBOLS["mcmcx_set_target_expdata_all"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, _DP])
+SYMBOLS["mcmcx_chain_data_info"] = (C.c_int, [C.c_void_p, _LP])
 
 _lib = None
 

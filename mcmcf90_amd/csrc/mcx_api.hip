@@ -209,6 +209,47 @@ int mcmcx_start_info(mcmcx_handle h, int64_t *out3)
     out3[0] = h->start_mode; out3[1] = h->start_redrew; out3[2] = h->start_fell;
     return 0;
 }
+// ---- a data set per chain (include/mcmcx.h, "Many fits in one run"): the response-column target with every chain's own observations.
+// Every target setter drops what an earlier mcmcx_set_target_expdata_all left: the last setter called wins.
+static void drop_chain_data(mcmcx_engine *h)
+{
+    h->cdata_mode = 0; h->cdata_n = 0;
+    std::vector<double>().swap(h->ty_all); std::vector<double>().swap(h->tx_all);
+}
+int mcmcx_set_target_expdata_all(mcmcx_handle h, int32_t nchains, int32_t ndata, int32_t nycol, const double *x, int32_t x_per_chain,
+                                 const double *y_all)
+{
+    const char *who = "mcmcx_set_target_expdata_all";
+    if (!h) return fail(-58, std::string(who) + ": null handle");
+    if (h->inited) return fail(-58, std::string(who) + " after mcmcx_init (the data tables are filled there)");
+    if (!x || !y_all) return fail(-58, std::string(who) + ": null array");
+    if (nchains != h->cfg.nchains) return fail(-58, std::string(who) + ": y_all has " + std::to_string(nchains) +
+        " data sets but the handle has nchains = " + std::to_string(h->cfg.nchains));
+    if (ndata < 1) return fail(-58, std::string(who) + ": ndata must be >= 1");
+    if (x_per_chain != 0 && x_per_chain != 1) return fail(-58, std::string(who) + ": x_per_chain must be 0 or 1");
+    if (h->pooled) return fail(-58, std::string(who) + ": not in pooled mode (one proposal factor pooled over different posteriors is not "
+        "a method)");
+    if (nycol < 1 || nycol > MCX_MAX_NYCOL) return fail(-21, "nycol must be in 1.." + std::to_string(MCX_MAX_NYCOL));
+    if (h->d != 1 + nycol) return fail(-22, "response-column target needs npar = 1 + nycol");
+    drop_chain_data(h);
+    const size_t N = (size_t)nchains, n = (size_t)ndata;
+    h->tkind = TGT_EXPCOLS; h->tncols = nycol;
+    h->cdata_mode = x_per_chain ? 2 : 1; h->cdata_n = ndata;
+    h->ty_all.assign(y_all, y_all + N * (size_t)nycol * n);
+    std::vector<double>().swap(h->ty);
+    if (x_per_chain) { h->tx_all.assign(x, x + N * n); std::vector<double>().swap(h->tx); }
+    else h->tx.assign(x, x + n);
+    return 0;
+}
+int mcmcx_chain_data_info(mcmcx_handle h, int64_t *out4)
+{
+    if (!h || !h->inited) return fail(-40, "we have not inited");
+    if (!out4) return fail(-1, "mcmcx_chain_data_info: null argument");
+    const bool data = h->tkind == TGT_EXPDATA || h->tkind == TGT_EXPCOLS;
+    out4[0] = h->cdata_mode; out4[1] = data ? h->E.tgt.ndata : 0; out4[2] = !data ? 0 : h->tkind == TGT_EXPCOLS ? h->tncols : 1;
+    out4[3] = h->cdata_bytes;
+    return 0;
+}
 int mcmcx_set_cmat0(mcmcx_handle h, const double *c, int32_t n)
 {
     if (!h || !c) return fail(-1, "null argument");
@@ -228,21 +269,21 @@ int mcmcx_set_sigma2nobs(mcmcx_handle h, const double *s2, const int32_t *nobs, 
 int mcmcx_set_target_gauss(mcmcx_handle h, const double *mu, const double *lam)
 {
     if (!h || !mu || !lam) return fail(-1, "null argument");
-    h->tkind = TGT_GAUSS; h->tmu.assign(mu, mu + h->d); h->tlam.assign(lam, lam + (size_t)h->d * h->d);
+    drop_chain_data(h); h->tkind = TGT_GAUSS; h->tmu.assign(mu, mu + h->d); h->tlam.assign(lam, lam + (size_t)h->d * h->d);
     return 0;
 }
 int mcmcx_set_target_banana(mcmcx_handle h, double b)
 {
     if (!h) return fail(-1, "null handle");
     if (h->d < 2) return fail(-22, "banana target needs npar >= 2");
-    h->tkind = TGT_BANANA; h->tb = b;
+    drop_chain_data(h); h->tkind = TGT_BANANA; h->tb = b;
     return 0;
 }
 int mcmcx_set_target_expdata(mcmcx_handle h, int32_t n, const double *x, const double *y)
 {
     if (!h || !x || !y || n < 1) return fail(-1, "bad argument");
     if (h->d != 2) return fail(-22, "expdata target needs npar = 2");
-    h->tkind = TGT_EXPDATA; h->tx.assign(x, x + n); h->ty.assign(y, y + n);
+    drop_chain_data(h); h->tkind = TGT_EXPDATA; h->tx.assign(x, x + n); h->ty.assign(y, y + n);
     return 0;
 }
 int mcmcx_set_target_expdata_cols(mcmcx_handle h, int32_t n, int32_t nycol, const double *x, const double *y)
@@ -250,13 +291,13 @@ int mcmcx_set_target_expdata_cols(mcmcx_handle h, int32_t n, int32_t nycol, cons
     if (!h || !x || !y || n < 1) return fail(-1, "bad argument");
     if (nycol < 1 || nycol > MCX_MAX_NYCOL) return fail(-21, "nycol must be in 1.." + std::to_string(MCX_MAX_NYCOL));
     if (h->d != 1 + nycol) return fail(-22, "response-column target needs npar = 1 + nycol");
-    h->tkind = TGT_EXPCOLS; h->tncols = nycol; h->tx.assign(x, x + n); h->ty.assign(y, y + (size_t)n * nycol);
+    drop_chain_data(h); h->tkind = TGT_EXPCOLS; h->tncols = nycol; h->tx.assign(x, x + n); h->ty.assign(y, y + (size_t)n * nycol);
     return 0;
 }
 int mcmcx_set_target_host(mcmcx_handle h, mcmcx_ssfun_t ss, mcmcx_priorfun_t pri, mcmcx_checkbounds_t cb, void *user)
 {
     if (!h || !ss) return fail(-1, "mcmcx_set_target_host: ssfunction is required");     // ssfunction0.f90:10-14
-    h->tkind = TGT_HOST; h->h_ss = ss; h->h_ss_batch = nullptr; h->h_pri = pri; h->h_cb = cb; h->h_user = user;
+    drop_chain_data(h); h->tkind = TGT_HOST; h->h_ss = ss; h->h_ss_batch = nullptr; h->h_pri = pri; h->h_cb = cb; h->h_user = user;
     return 0;
 }
 
@@ -265,7 +306,7 @@ int mcmcx_set_target_host_batch(mcmcx_handle h, mcmcx_ssfun_batch_t ss_batch, mc
 {
     if (!h || !ss_batch) return fail(-1, "mcmcx_set_target_host_batch: ssfunction_batch is required");
     if (h->inited) return fail(-20, "set the target before mcmcx_init");
-    h->tkind = TGT_HOST; h->h_ss_batch = ss_batch; h->h_ss = nullptr; h->h_pri = pri; h->h_cb = cb; h->h_user = user;
+    drop_chain_data(h); h->tkind = TGT_HOST; h->h_ss_batch = ss_batch; h->h_ss = nullptr; h->h_pri = pri; h->h_cb = cb; h->h_user = user;
     h->h_threads = nthreads < 1 ? 1 : nthreads;
     return 0;
 }
@@ -274,6 +315,7 @@ int mcmcx_set_target_external(mcmcx_handle h)
 {
     if (!h) return fail(-1, "null handle");
     if (h->inited) return fail(-2, "mcmcx_set_target_external after mcmcx_init");
+    drop_chain_data(h);
     h->tkind = TGT_HOST; h->h_ss = nullptr; h->h_ss_batch = nullptr; h->h_pri = nullptr; h->h_cb = nullptr; h->h_user = nullptr;
     h->external = true;
     return 0;
@@ -325,7 +367,7 @@ int mcmcx_set_target_module(mcmcx_handle h, const char *code_object_path, const 
         h->allocs.push_back(h->d_moddata);
         HIPCHK(hipMemcpy(h->d_moddata, userdata, (size_t)nbytes, hipMemcpyHostToDevice));
     }
-    h->tkind = TGT_MODULE;
+    drop_chain_data(h); h->tkind = TGT_MODULE;
     return 0;
 }
 
@@ -431,7 +473,7 @@ static int init_engine_dev(mcmcx_engine *h, const InitialFactor &f)    // Engine
     E.dr_lds = h->plan.dr_lds ? 1 : 0;
     E.lds_scratch = h->plan.lds_form;
     E.tgt.kind = phased(h) ? (int)TGT_HOST : h->tkind;   // the kernels know one phase-cut mode; who evaluates is the host's business
-    E.tgt.b = h->tb; E.tgt.ndata = (int)h->tx.size(); E.tgt.ncols = h->tncols;
+    E.tgt.b = h->tb; E.tgt.ndata = h->cdata_mode ? h->cdata_n : (int)h->tx.size(); E.tgt.ncols = h->tncols;
     const int d = h->d;
     int rc;
     if (h->tkind == TGT_GAUSS) {
@@ -440,8 +482,17 @@ static int init_engine_dev(mcmcx_engine *h, const InitialFactor &f)    // Engine
         for (int i = 0; i < d; ++i) for (int j = 0; j < d; ++j) lt[(size_t)j * d + i] = h->tlam[(size_t)i * d + j];
         if ((rc = dev_upload(h, &E.tgt.lamT, lt))) return rc;
     }
-    if (h->tkind == TGT_EXPDATA || h->tkind == TGT_EXPCOLS) { if ((rc = dev_upload(h, &E.tgt.x, h->tx))) return rc; if ((rc = dev_upload(h,
-        &E.tgt.y, h->ty))) return rc; }
+    if (h->cdata_mode) {                                 // a data set per chain: init_chain_data's tables, and the shared x where kept
+        const size_t L = (size_t)h->ntiles * 64, n = (size_t)h->cdata_n;
+        double *yc = nullptr, *xc = nullptr;
+        if ((rc = dev_alloc(h, &yc, L * (size_t)h->tncols * n, false))) return rc;
+        if (h->cdata_mode == 2 ? (rc = dev_alloc(h, &xc, L * n, false)) : (rc = dev_upload(h, &E.tgt.x, h->tx))) return rc;
+        E.tgt.yc = yc; E.tgt.xpc = xc ? 1 : 0;
+        if (xc) E.tgt.xc = xc;
+        h->cdata_bytes = (long long)((L * (size_t)h->tncols * n + (xc ? L * n : 0)) * sizeof(double));
+    } else if (h->tkind == TGT_EXPDATA || h->tkind == TGT_EXPCOLS) {
+        if ((rc = dev_upload(h, &E.tgt.x, h->tx)) || (rc = dev_upload(h, &E.tgt.y, h->ty))) return rc;
+    }
     if (h->has_lo && (rc = dev_upload(h, &E.tgt.lo, h->tlo))) return rc;
     if (h->has_hi && (rc = dev_upload(h, &E.tgt.hi, h->thi))) return rc;
     if (h->has_pri) { if ((rc = dev_upload(h, &E.tgt.pmu, h->tpmu))) return rc; if ((rc = dev_upload(h, &E.tgt.psig, h->tpsig))) return rc;
@@ -581,6 +632,29 @@ static int init_starts(mcmcx_engine *h, const InitialFactor &f)
     }
     return 0;
 }
+// E.tgt.yc / xc, when every chain has a data set of its own: the call's rows staged into tiles, yc [tile][j * ndata + i][64] and (mode 2)
+// xc [tile][i][64] with 64-bit indices; lanes of the last tile without a chain hold +0.0.  The host copies of the call are released here.
+static int init_chain_data(mcmcx_engine *h)
+{
+    EngineDev &E = h->E;
+    const size_t T = (size_t)h->ntiles, N = (size_t)h->cfg.nchains, n = (size_t)h->cdata_n, rows = (size_t)h->tncols * n;
+    {
+        std::vector<double> st(T * rows * 64, 0.0);
+        for (size_t c = 0; c < N; ++c)
+            for (size_t r = 0; r < rows; ++r) st[((c / 64) * rows + r) * 64 + (c % 64)] = h->ty_all[c * rows + r];
+        HIPCHK(hipMemcpyAsync(const_cast<double *>(E.tgt.yc), st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if (h->cdata_mode == 2) {
+        std::vector<double> st(T * n * 64, 0.0);
+        for (size_t c = 0; c < N; ++c)
+            for (size_t i = 0; i < n; ++i) st[((c / 64) * n + i) * 64 + (c % 64)] = h->tx_all[c * n + i];
+        HIPCHK(hipMemcpyAsync(const_cast<double *>(E.tgt.xc), st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    std::vector<double>().swap(h->ty_all); std::vector<double>().swap(h->tx_all);
+    return 0;
+}
 static int fill_start(mcmcx_engine *h, double *dst)         // dst = every chain's start: par0, or its row of E.start
 {
     if (!h->E.start) return dev_bcast(h, dst, h->par0);
@@ -610,6 +684,7 @@ static int init_fill(mcmcx_engine *h, const InitialFactor &f)
     HIPCHK(hipStreamSynchronize(h->stream));
     int rc;
     if (h->start_mode && (rc = init_starts(h, f))) return rc;
+    if (h->cdata_mode && (rc = init_chain_data(h))) return rc;
     if ((rc = fill_start(h, E.theta))) return rc;
     if (!h->pooled && (rc = dev_bcast(h, E.R, f.Rp))) return rc;
     if (h->dodr && !h->pooled && ((rc = dev_bcast(h, E.R2, f.R2p)) || (rc = dev_bcast(h, E.iC, f.iCp)))) return rc;

@@ -31,11 +31,18 @@ struct DevTarget {
     const double *mu, *lamT;    // gauss: mean[d] and the precision matrix transposed, lamT[j*d+i] = lam(i,j) (padded)
     double b;                   // banana
     int ndata;                  // expdata
-    const double *x, *y;        // y: [ncols][ndata] for the response-column target
+    // y: [ncols][ndata] for the response-column target.  A data set per chain (mcmcx_set_target_expdata_all; the PCD instances of
+    // mcx_phase.hpp): the same two slots hold the tile-interleaved tables, yc [tile][ncols * ndata][64] with row j * ndata + i and
+    // -- xpc = 1 -- xc [tile][ndata][64]; xpc = 0: x stays the shared x[ndata].  (The table pointers share the slots and the flag stands
+    // in the padding after ncols, so that the kernel-argument layout of every other kernel is what it was.)
+    union { const double *x; const double *xc; };
+    union { const double *y; const double *yc; };
     int ncols;
+    int xpc;
     const double *lo, *hi;      // box bounds or nullptr
     const double *pmu, *psig;   // Gaussian priors or nullptr
 };
+static_assert(sizeof(DevTarget) == 96, "DevTarget is part of every kernel's argument block: a change of its layout moves all of them");
 
 struct EngineDev {
     int d, P, ntiles;

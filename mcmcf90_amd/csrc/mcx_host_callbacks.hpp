@@ -13,7 +13,9 @@ static int host_eval(mcmcx_engine *h, const double *dev_src, int stride_k, bool 
 {
     const int d = h->d, T = h->ntiles;
     if (h->tkind == TGT_EXPCOLS) {                      // device-resident response-column target: no host round trip
-        hipLaunchKernelGGL(dev_eval_kernel, dim3(T), dim3(64), 0, h->stream, h->E, dev_src, stride_k, use_stage2_flag ? 1 : 0, what);
+        const int s2 = use_stage2_flag ? 1 : 0;
+        if (h->cdata_mode) hipLaunchKernelGGL(dev_eval_kernel<true>, dim3(T), dim3(64), 0, h->stream, h->E, dev_src, stride_k, s2, what);
+        else hipLaunchKernelGGL(dev_eval_kernel, dim3(T), dim3(64), 0, h->stream, h->E, dev_src, stride_k, s2, what);
         HIPCHK(hipGetLastError());
         return 0;
     }

@@ -147,6 +147,9 @@ struct mcmcx_engine {
     double sigma2 = 1.0; int nobs = 1; bool sigma2ok = false;
     int ny = 1; std::vector<double> sigma2v; std::vector<int> nobsv;      // nycol columns (host callbacks only when > 1)
     int tkind = -1, tncols = 1; std::vector<double> tmu, tlam, tx, ty, tlo, thi, tpmu, tpsig; double tb = 0.1;
+    // a data set per chain (mcmcx_set_target_expdata_all): 0 one data set for all chains, 1 y per chain, 2 x and y per chain; the call's
+    // copies y_all [nchains][tncols][ndata] and (mode 2) x_all [nchains][ndata] until init_chain_data has filled the device tables
+    int cdata_mode = 0, cdata_n = 0; std::vector<double> ty_all, tx_all; long long cdata_bytes = 0;
     bool has_lo = false, has_hi = false, has_pri = false;
     mcmcx_ssfun_t h_ss = nullptr; mcmcx_ssfun_er_t h_ss_er = nullptr; mcmcx_priorfun_t h_pri = nullptr; mcmcx_checkbounds_t h_cb = nullptr;
         void *h_user = nullptr;

@@ -309,6 +309,14 @@ static void launch_group_ram(mcmcx_engine *h, int it0, int it1)
 static const KernelEntry STEP_TABLE[] = {
     // ---- a device target with response columns (nycol >= 1 sums of squares per point): the phases of an iteration in one launch
     // (one instantiation per method class: MCMC_run_ram's carries the rank-one update's panels, the others do not)
+    // (a data set per chain, mcmcx_set_target_expdata_all: the same kernels with the evaluations' data loads per lane; never pooled)
+    {"step", "step_kernel_cols<ram, pcd>", [](const mcmcx_engine *h) {
+        return h->plan.fused_cols && kernel_method(h) == M_RAM && h->cdata_mode != 0; },
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel_cols<1, true>), G1, lds_step(h), STEP_ARGS,
+         (const double *)h->d_ramscale, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
+    {"step", "step_kernel_cols<pcd>", [](const mcmcx_engine *h) { return h->plan.fused_cols && h->cdata_mode != 0; },
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel_cols<0, true>), G1, lds_step(h), STEP_ARGS,
+         (const double *)h->d_ramscale, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
     {"step", "step_kernel_cols<ram>", [](const mcmcx_engine *h) { return h->plan.fused_cols && kernel_method(h) == M_RAM; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<1>, G1, lds_step(h), STEP_ARGS,
          (const double *)h->d_ramscale, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
@@ -420,6 +428,9 @@ static int scam_tile_waves(const mcmcx_engine *h, const mcx_switches &sw)
 #define SCAM_POOLED_ARGS ScamPooledLds(h->d).bytes, h->stream, h->E, it0, it1, h->E.tgt.mu, h->E.tgt.lamT
 // (SH_UREP: the per-chain kernels read every chain's own rotation, E.Rf / E.qstd -- in pooled mode above npar 240, copies of the one)
 static const KernelEntry SCAM_TABLE[] = {
+    {"scam", "step_kernel_cols<scam, pcd>", [](const mcmcx_engine *h) { return h->plan.fused_cols && !h->pooled && h->cdata_mode != 0; },
+     [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL((step_kernel_cols<2, true>), G1, 0, STEP_ARGS,
+         (const double *)h->d_ramscale, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},
     {"scam", "step_kernel_cols<scam>", [](const mcmcx_engine *h) { return h->plan.fused_cols && !h->pooled; },
      [](mcmcx_engine *h, int it0, int it1) { hipLaunchKernelGGL(step_kernel_cols<2>, G1, 0, STEP_ARGS, (const double *)h->d_ramscale,
          (const double *)nullptr, (const double *)nullptr, (const double *)nullptr); }},

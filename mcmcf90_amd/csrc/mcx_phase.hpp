@@ -88,6 +88,9 @@ MCX_DEV void host_finish(const EngineDev &E, int tile, int lane, int it, LaneSta
 //   ss_j(theta) = sum_i (y_j(i) - theta_1 exp(-theta_{1+j} x_i))**2,  j = 1..nycol  (oracle/mcx_targets.h: mcxt_ss_expdata_cols)
 // with the library's box bounds and Gaussian priors.  what: 0 = checkbounds, priorfun, ssfunction; 1 = checkbounds and
 // priorfun; 2 = ssfunction alone (ssfunction_er0.f90: the default ssfunction_er is ssfunction).
+// PCD: a data set per chain (mcmcx_set_target_expdata_all) -- y_j(i), and with E.tgt.xpc x_i too, are the lane's own elements of its tile's
+// rows (one 512-byte segment per wave load) instead of the shared arrays' scalar loads; the fma chain of every ss_j is the same statement.
+template <bool PCD = false>
 MCX_DEV void dev_eval_body(const EngineDev &E, int tile, int lane, const double *src, int stride_k, int use_stage2, int what)
 {
     const int d = E.d, ny = E.ny;
@@ -107,10 +110,27 @@ MCX_DEV void dev_eval_body(const EngineDev &E, int tile, int lane, const double 
         double ss = 0.0;
         if (doss) {
             const double thj = GV(c_t, 1 + j);
-            const double *yj = E.tgt.y + (size_t)j * E.tgt.ndata;
-            for (int i = 0; i < E.tgt.ndata; ++i) {
-                double r = yj[i] - th0 * d_exp(-(thj * E.tgt.x[i]));
-                ss = dfma(r, r, ss);
+            if constexpr (PCD) {
+                const size_t nd = (size_t)E.tgt.ndata;
+                const double *yj = E.tgt.yc + ((size_t)tile * ny + j) * nd * 64;
+                if (E.tgt.xpc) {
+                    const double *xt = E.tgt.xc + (size_t)tile * nd * 64;
+                    for (int i = 0; i < E.tgt.ndata; ++i) {
+                        double r = GV(yj, i) - th0 * d_exp(-(thj * GV(xt, i)));
+                        ss = dfma(r, r, ss);
+                    }
+                } else {
+                    for (int i = 0; i < E.tgt.ndata; ++i) {
+                        double r = GV(yj, i) - th0 * d_exp(-(thj * E.tgt.x[i]));
+                        ss = dfma(r, r, ss);
+                    }
+                }
+            } else {
+                const double *yj = E.tgt.y + (size_t)j * E.tgt.ndata;
+                for (int i = 0; i < E.tgt.ndata; ++i) {
+                    double r = yj[i] - th0 * d_exp(-(thj * E.tgt.x[i]));
+                    ss = dfma(r, r, ss);
+                }
             }
         }
         GV(hev, HE_SS + j) = ss;
@@ -120,6 +140,10 @@ MCX_DEV void dev_eval_body(const EngineDev &E, int tile, int lane, const double 
 }
 __global__ __launch_bounds__(64) void dev_eval_kernel(EngineDev E, const double *__restrict__ src, int stride_k, int use_stage2, int what)
 { dev_eval_body(E, blockIdx.x, threadIdx.x, src, stride_k, use_stage2, what); }
+// (the per-chain-data instance, dev_eval_kernel<true>, is an overload of its own: the shared-data kernel keeps its symbol and its code)
+template <bool PCD>
+__global__ __launch_bounds__(64) void dev_eval_kernel(EngineDev E, const double *__restrict__ src, int stride_k, int use_stage2, int what)
+{ dev_eval_body<PCD>(E, blockIdx.x, threadIdx.x, src, stride_k, use_stage2, what); }
 
 // sR / sR2 / siC: pooled mode's shared factor, second-stage factor and inverse covariance (nullptr: the chain's own)
 // PROPOSE = false: phase 1 leaves the second stage's normals and proposal to its caller (pooled_phase_mfma_kernel: on the matrix cores)
@@ -335,46 +359,62 @@ __global__ __launch_bounds__(64) void host_phase_seq_kernel(EngineDev E, int itA
 #ifndef MCX_COLS_WAVES
 #define MCX_COLS_WAVES 2
 #endif
+// The kernel's text is stated once, as a macro over the evaluation it calls: the shared-data kernels step_kernel_cols<MSEL> keep their
+// symbols and compile to what they were (profiles/kernel_resources.txt; a device function between kernel and phases moved their register
+// allocation), and the per-chain-data instances step_kernel_cols<MSEL, true> (mcmcx_set_target_expdata_all: every evaluation of the
+// launch reads the chain's own data set) are overloads beside them.  In the text:
+//   MSEL == 2: MCMC_run_scam.F90:94-138, npar componentwise proposals, each with its own evaluation;
+//   method 'er': MCMC_run_er.F90:54-101, the threshold is drawn between priorfun and ssfunction;
+//   the tail: pooled method = 'ram' -- the tick's statistic reads the last iteration's normals where the single-launch kernels leave them,
+//   in the (it & 1) half of the chain's two normal vectors (moments_kernel kind 2); the phases keep stage-1 normals in the first half.
+#define MCX_STEP_COLS_TEXT(EVAL)                                                                                                       \
+    extern __shared__ double X[];                                                                                                      \
+    const int lane = threadIdx.x, tile = blockIdx.x, d = E.d;                                                                          \
+    for (int it = it0; it <= it1; ++it) {                                                                                              \
+        const double *rs = ramscale + it;                                                                                              \
+        if constexpr (MSEL == 2) {                                                                                                     \
+            for (int j = 0; j < d; ++j) {                                                                                              \
+                host_phase_body<5, MSEL>(E, tile, lane, it, rs, j, X);                                                                 \
+                EVAL(E, tile, lane, E.cand, d, 0, 0);                                                                                  \
+                host_phase_body<6, MSEL>(E, tile, lane, it, rs, j, X);                                                                 \
+            }                                                                                                                          \
+            host_phase_body<7, MSEL>(E, tile, lane, it, rs, 0, X);                                                                     \
+        } else {                                                                                                                       \
+            host_phase_body<0, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);                                                       \
+            if (MSEL == 0 && E.method == M_ER) {                                                                                       \
+                EVAL(E, tile, lane, E.cand, d, 0, 1);                                                                                  \
+                host_phase_body<3, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);                                                   \
+                EVAL(E, tile, lane, E.cand, d, 1, 2);                                                                                  \
+                host_phase_body<4, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);                                                   \
+                continue;                                                                                                              \
+            }                                                                                                                          \
+            EVAL(E, tile, lane, E.cand, d, 0, 0);                                                                                      \
+            host_phase_body<1, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);                                                       \
+            if (MSEL == 0 && E.dodr) {                                                                                                 \
+                EVAL(E, tile, lane, E.cs, 2 * d, 1, 0);                                                                                \
+                host_phase_body<2, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);                                                   \
+            }                                                                                                                          \
+        }                                                                                                                              \
+    }                                                                                                                                  \
+    if (MSEL != 2 && sR && !E.dodr && (it1 & 1)) {                                                                                     \
+        double *zs_t = E.zs + (size_t)tile * 2 * d * 64;                                                                               \
+        for (int k = 0; k < d; ++k) GV(zs_t, d + k) = GV(zs_t, k);                                                                     \
+    }
 template <int MSEL>
 __global__ __launch_bounds__(64, MCX_COLS_WAVES) void step_kernel_cols(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
                                                                        const double *__restrict__ sR, const double *__restrict__ sR2,
                                                                        const double *__restrict__ siC)
 {
-    extern __shared__ double X[];
-    const int lane = threadIdx.x, tile = blockIdx.x, d = E.d;
-    for (int it = it0; it <= it1; ++it) {
-        const double *rs = ramscale + it;
-        if constexpr (MSEL == 2) {                      // MCMC_run_scam.F90:94-138: npar componentwise proposals, each with its own evaluation
-            for (int j = 0; j < d; ++j) {
-                host_phase_body<5, MSEL>(E, tile, lane, it, rs, j, X);
-                dev_eval_body(E, tile, lane, E.cand, d, 0, 0);
-                host_phase_body<6, MSEL>(E, tile, lane, it, rs, j, X);
-            }
-            host_phase_body<7, MSEL>(E, tile, lane, it, rs, 0, X);
-        } else {
-            host_phase_body<0, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);
-            if (MSEL == 0 && E.method == M_ER) {        // MCMC_run_er.F90:54-101: the threshold is drawn between priorfun and ssfunction
-                dev_eval_body(E, tile, lane, E.cand, d, 0, 1);
-                host_phase_body<3, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);
-                dev_eval_body(E, tile, lane, E.cand, d, 1, 2);
-                host_phase_body<4, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);
-                continue;
-            }
-            dev_eval_body(E, tile, lane, E.cand, d, 0, 0);
-            host_phase_body<1, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);
-            if (MSEL == 0 && E.dodr) {
-                dev_eval_body(E, tile, lane, E.cs, 2 * d, 1, 0);
-                host_phase_body<2, MSEL>(E, tile, lane, it, rs, 0, X, sR, sR2, siC);
-            }
-        }
-    }
-    // pooled method = 'ram': the tick's statistic reads the last iteration's normals where the single-launch kernels leave them,
-    // in the (it & 1) half of the chain's two normal vectors (moments_kernel kind 2); the phases keep stage-1 normals in the first half
-    if (MSEL != 2 && sR && !E.dodr && (it1 & 1)) {
-        double *zs_t = E.zs + (size_t)tile * 2 * d * 64;
-        for (int k = 0; k < d; ++k) GV(zs_t, d + k) = GV(zs_t, k);
-    }
+    MCX_STEP_COLS_TEXT(dev_eval_body)
 }
+template <int MSEL, bool PCD>
+__global__ __launch_bounds__(64, MCX_COLS_WAVES) void step_kernel_cols(EngineDev E, int it0, int it1, const double *__restrict__ ramscale,
+                                                                       const double *__restrict__ sR, const double *__restrict__ sR2,
+                                                                       const double *__restrict__ siC)
+{
+    MCX_STEP_COLS_TEXT(dev_eval_body<PCD>)
+}
+#undef MCX_STEP_COLS_TEXT
 
 // ---------------------------------------------------------------- MCMC_run1 / MCMC_run1_er: one evaluation per invocation
 // The reference's file protocol (MCMC_run1.F90:31-256, MCMC_run1_er.F90:28-234) keeps the chain's state in files between

@@ -38,6 +38,32 @@ def make_config(npar, nchains=1, **kw):
     return c
 
 
+def chain_data_arrays(nchains, npar, xdata, ydata):
+    """(x, y, nycol, x_per_chain) for Engine.set_target_all: y as a contiguous float64 (nchains, nycol, ndata) from ydata (nchains, nycol,
+    ndata) or (nchains, ndata), x as a contiguous float64 (ndata,) -- x_per_chain = 0 -- or (nchains, ndata) -- 1.  Raises ValueError on
+    shapes that do not fit nchains, npar = 1 + nycol or each other; no library call."""
+    x, y = _f64(xdata), _f64(ydata)
+    nchains, npar = int(nchains), int(npar)
+    if y.ndim == 2:
+        if npar != 2:
+            raise ValueError("ydata is (nchains, ndata): one response column needs npar = 2, got npar = %d" % npar)
+        y = y.reshape(y.shape[0], 1, y.shape[1])
+    if y.ndim != 3:
+        raise ValueError("ydata must be (nchains, nycol, ndata) or (nchains, ndata), got %s" % (y.shape,))
+    if y.shape[0] != nchains:
+        raise ValueError("ydata holds %d data sets, the engine has %d chains" % (y.shape[0], nchains))
+    nycol, ndata = y.shape[1], y.shape[2]
+    if nycol < 1 or ndata < 1:
+        raise ValueError("ydata must hold at least one column and one observation, got %s" % (y.shape,))
+    if npar != 1 + nycol:
+        raise ValueError("the model has npar = 1 + nycol parameters: npar = %d, nycol = %d" % (npar, nycol))
+    if x.shape == (ndata,):
+        return x, y, nycol, 0
+    if x.shape == (nchains, ndata):
+        return x, y, nycol, 1
+    raise ValueError("xdata must be (ndata,) = (%d,) or (nchains, ndata) = (%d, %d), got %s" % (ndata, nchains, ndata, x.shape))
+
+
 def sample_iterations(first, thin, capacity, simuind):
     """The iterations a sample store retains once the run stands at `simuind` (mcmcx_set_samples' rule, stated once): iteration i,
     1 <= i <= simuind, is kept when i >= first and (i - first) % thin == 0, and the ring holds the last `capacity` of those.
@@ -354,6 +380,18 @@ class Engine:
                 self._chk(self.L.mcmcx_set_target_expdata(self.h, x.size, _dp(x), _dp(y)))
         else:
             raise KeyError(kind)
+
+    def set_target_all(self, xdata, ydata):
+        """Many fits in one run (mcmcx_set_target_expdata_all): the "expdata" model with a data set per chain.  ydata is
+        (nchains, nycol, ndata), or (nchains, ndata) for one column; xdata is (ndata,), shared, or (nchains, ndata).  Before init."""
+        x, y, nycol, x_per_chain = chain_data_arrays(self.nchains, self.npar, xdata, ydata)
+        self._chk(self.L.mcmcx_set_target_expdata_all(self.h, y.shape[0], y.shape[2], nycol, _dp(x), x_per_chain, _dp(y)))
+
+    def chain_data_info(self):
+        """After init: whose data the chains fit (mcmcx_chain_data_info); `bytes` are the per-chain device tables'."""
+        a = np.zeros(4, dtype=np.int64)
+        self._chk(self.L.mcmcx_chain_data_info(self.h, a.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(mode=("shared", "y_per_chain", "xy_per_chain")[int(a[0])], ndata=int(a[1]), nycol=int(a[2]), bytes=int(a[3]))
 
     def set_target_host(self, ssfun, priorfun=None, checkbounds=None, ssfun_er=None):
         """User callbacks on the host, like the reference's link-time ssfunction / priorfun / checkbounds:
